@@ -1,8 +1,19 @@
 """Headline benchmark: training images/sec of the plastic U-Net (BASELINE.json metric), MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the
+outputs of the last timed step if --dump-outputs is given, and the result line.  Every other
+measurement (the blocks listed below) takes passes of its own and runs only with --full; in a plain
+run those blocks are null.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, rank 0's copy, as
+DIR/loss.npy (the step's mean BCE) and DIR/hebb.npy (the plastic traces [B,N,N] after the step), in
+float32, 64 MB at most in all (a fixed, seeded sample of an array that would not fit).  The model's
+initialisation and the synthetic batches are seeded, so the same arguments give the same inputs in
+every run and two builds can be compared output for output.
 
 Without a launcher (no WORLD_SIZE in the environment), --gpus N > 1 makes this process spawn N
 rank processes itself (launch_workers: torchrun's env, MASTER_ADDR 127.0.0.1, a free port) and
@@ -17,7 +28,7 @@ with Dropout2d active) - parity/coverage lines, not the headline.  A step = forw
 plastic traces carried step to step.  Timed region: barrier + synchronize on both sides, max over
 ranks; value = images of all ranks / time (weak scaling: 32 images per GPU).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  Besides the contract fields it carries, with --full,
   roofline      the dominant kernel's algorithmic TFLOP/s vs the fp32 MFMA peak, from HIP events
                 bracketing each launch on its own stream during a separate instrumented pass
   kernels       per-kernel-instantiation time/FLOP breakdown of one step
@@ -56,10 +67,15 @@ def parse():
     ap.add_argument("--rule", default="oja")
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--steplr", type=float, default=1e5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (loss, hebb) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline figure: all-reduce accounting, per-kernel "
+                         "profile and roofline, Oja-update bandwidth, CPU baseline (each in passes of its own)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample length (per mode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-profile", action="store_true")
-    ap.add_argument("--no-oja", action="store_true", help="skip the Oja-update HBM benchmark")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="with --full: skip the per-kernel pass")
+    ap.add_argument("--no-oja", action="store_true", help="with --full: skip the Oja-update HBM benchmark")
     ap.add_argument("--graph", choices=["on", "off"], default="off",
                     help="on: fwd + BCE + bwd captured once as a HIP graph and replayed (one rank only). "
                          "Off by default: measured no faster on C2 / C4 and slower on C3, whose replay loses "
@@ -222,6 +238,26 @@ def oja_update_bench(K, B, N, device, feat_channels=64):
     return res
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: all arrays together
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy, float32 (float64 stays float64).  An array over its
+    share of DUMP_BYTES is stored as a fixed sample: the elements at sorted indices drawn without
+    replacement by numpy's default_rng(0), the same in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        a = (t if t.dtype == torch.float64 else t.float()).contiguous().numpy()
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -330,13 +366,17 @@ def main():
         per_rank = [x.item() for x in ts_all]
         elapsed = max(per_rank)
     final_loss = loss.item() if loss is not None else float("nan")
+    if args.dump_outputs and rank == 0 and loss is not None:
+        dump_outputs(args.dump_outputs, {"loss": loss, "hebb": hebb})
 
     # ---------------- all-reduce accounting (untimed pass): buckets issued, issued during the
     # backward (overlapped), bucket sizes, and the exposed all-reduce time per step - the compute
     # stream's wait between the last backward kernel and Adam (HIP events, punet/engine.py)
     allreduce = {"active": False, "world": world,
                  "note": "single rank: no gradient exchange (the reducer is off at world 1)"}
-    if trainer.reducer is not None:
+    if trainer.reducer is not None and not args.full:
+        allreduce = None      # the exchange runs in every step; its accounting pass is --full's
+    if args.full and trainer.reducer is not None:
         trainer.measure_allreduce = True
         trainer.allreduce_log = []
         for i in range(max(2, min(5, args.steps))):
@@ -355,7 +395,7 @@ def main():
     # ---------------- instrumented pass: per-launch HIP events on the launching stream
     kern = None
     roof = None
-    if not args.no_kernel_profile:
+    if args.full and not args.no_kernel_profile:
         nprof = max(1, min(3, args.steps))
         # one stream for this pass: with the bf16 trunk's weight-gradient side stream (timed region
         # above) a launch's events would also time the kernels running beside it
@@ -438,11 +478,11 @@ def main():
                     roof["pmc_mfma_busy_frac"] = tr["mfma_busy_frac"]
 
     oja = None
-    if rank == 0 and not args.no_oja:
+    if args.full and rank == 0 and not args.no_oja:
         oja = oja_update_bench(K, B, S, device, feat_channels=net.outc.conv.weight.shape[1])
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, B)
 
     if rank == 0:

@@ -59,6 +59,21 @@ def test_world_mismatch_exits_nonzero():
     bench.check_world(2, 2, devices=8)     # consistent: returns
 
 
+def test_dump_outputs_samples_an_array_over_its_share(tmp_path, monkeypatch):
+    """An output larger than its share of the 64 MB is stored as a fixed, seeded sample;
+    float64 stays, every other dtype becomes float32."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 4 * 100)
+    big = torch.arange(1000, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path), {"big": big, "small": torch.ones(3, 5, dtype=torch.bfloat16)})
+    a, b = np.load(tmp_path / "big.npy"), np.load(tmp_path / "small.npy")
+    assert a.dtype == np.float64 and a.shape == (50,) and (np.diff(a) > 0).all()
+    assert b.dtype == np.float32 and b.shape == (3, 5)
+    bench.dump_outputs(str(tmp_path / "again"), {"big": big, "small": big[:2]})
+    assert (np.load(tmp_path / "again" / "big.npy") == a).all()
+
+
 def test_bench_gpus_n_without_devices_fails_fast():
     """On a box with fewer GPUs than --gpus the parent refuses before spawning anything."""
     env = dict(os.environ)

@@ -5,8 +5,8 @@ set -u
 VAR=$1; VALS=$2; shift 2
 for rep in 1 2; do
   for v in $VALS; do
-    log=gpurun_out/ab/$VAR.$(basename $v).log
-    mkdir -p gpurun_out/ab; env $VAR=$v timeout -k 10 240 python bench.py --no-cpu-baseline --no-oja "$@" > $log 2>&1 || { echo "bench failed ($VAR=$v)"; tail -20 $log; exit 1; }
+    log=${OUT:-bench_out/ab}/$VAR.$(basename $v).log
+    mkdir -p $(dirname $log); env $VAR=$v timeout -k 10 240 python bench.py --full --no-cpu-baseline --no-oja "$@" > $log 2>&1 || { echo "bench failed ($VAR=$v)"; tail -20 $log; exit 1; }
     out=$(grep "^{\"metric\"" $log | tail -1)
     python -c "
 import json,sys; d=json.loads(sys.argv[1]); r=d['roofline']

@@ -3,6 +3,7 @@
 // 8 lanes and with 1 KB contiguous per instruction.  Each "item" = a fixed compute delay
 // (s_sleep) + the stores; the next item's first wait is vmcnt(0) (the kernel's counted waits on
 // loads issued after the stores behave the same: vmcnt retires in issue order).
+//   hipcc -O3 --offload-arch=gfx950 tools/probes/store_pattern.hip -o tools/probes/store_pattern
 #include <hip/hip_runtime.h>
 #include <cstdio>
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile of the FINAL build, one GPU call:
-#   1. the C2 bench line (bench.py defaults)                          -> $OUT/c2.json
+#   1. the C2 bench line (bench.py --full)                  -> $OUT/c2.json
 #   2. rocprofv3 --kernel-trace --stats of the same command             -> $OUT/c2_stats/
 #   3. separate PMC passes (FETCH_SIZE / WRITE_SIZE / clock + MFMA busy; never combined with
 #      sys/runtime traces) and tools/pmc_traffic.py                      -> $OUT/pmc_traffic.json
@@ -12,7 +12,7 @@ TAG=${1:-r02}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="python bench.py"
+B="python bench.py --full"
 step() { echo "[$(date +%T)] $1" | tee -a $OUT/passes.log; }
 
 step "c2 bench"

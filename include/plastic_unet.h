@@ -436,7 +436,8 @@ int pu_bce_bwd(const float* y, const float* t, long long n, const float* grad_lo
  * step_size = lr/(1-beta1^t) and bc2_sqrt = sqrt(1-beta2^t) are computed by the caller.  The
  * hyper-parameters are the optimizer's Python doubles: 1-beta1 and 1-beta2 are formed in double and
  * then rounded to fp32, as ATen does with the Scalar arguments of lerp_/addcmul_ (forming 1-beta2
- * from an fp32-rounded beta2 = 0.999 would be 1.3e-5 off).
+ * from an fp32-rounded beta2 = 0.999 would be 1.3e-5 off).  An entry with numel == 0 is skipped and
+ * its pointers may be null (an empty torch tensor has no storage).
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
     float* param;

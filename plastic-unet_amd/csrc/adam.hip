@@ -88,8 +88,9 @@ extern "C" int pu_adam_multi(const pu_adam_tensor* tensors, int n_tensors, doubl
         int blocks = 0;
         while (i < n_tensors && b.count < ADAM_MAX_T) {
             const pu_adam_tensor& t = tensors[i++];
-            PU_REQUIRE(t.param && t.grad && t.exp_avg && t.exp_avg_sq && t.numel >= 0, "pu_adam_multi: tensor %d", i - 1);
-            if (t.numel == 0) continue;
+            PU_REQUIRE(t.numel >= 0, "pu_adam_multi: tensor %d", i - 1);
+            if (t.numel == 0) continue;     // an empty tensor has no storage: its pointers are null (torch)
+            PU_REQUIRE(t.param && t.grad && t.exp_avg && t.exp_avg_sq, "pu_adam_multi: tensor %d", i - 1);
             b.p[b.count] = t.param; b.g[b.count] = t.grad; b.m[b.count] = t.exp_avg; b.v[b.count] = t.exp_avg_sq;
             b.n[b.count] = t.numel;
             b.block_start[b.count] = blocks;

@@ -398,13 +398,16 @@ def test_fused_adam_matches_torch_adam():
         assert_close(b, a, rtol=1e-6, atol_rel=1e-6)
 
 
-@pytest.mark.parametrize("B,N", [(32, 128), (128, 128), (3, 50), (2, 200), (1, 512)])
+@pytest.mark.parametrize("B,N", [(32, 128), (128, 128), (3, 50), (2, 200), (1, 512),
+                                 # the 64-tile (>= 512 blocks) at ragged N: 72 = 64 + 8, 200 = 3 * 64 + 8
+                                 (128, 72), (32, 200)])
 @pytest.mark.parametrize("rule", [0, 1])
 def test_fused_head_trace_equals_two_launch_path(B, N, rule):
     """pu_plastic_fwd fuses the trace update into the GEMM (every block recomputes row 0 of its
     column tile).  It must equal, bit for bit, the GEMM followed by the stand-alone update on its
-    own Y (the in-place call takes that path), for both tile sizes (32: small grids, 64) and
-    ragged N."""
+    own Y, for both tile sizes (32: small grids, 64) and ragged N.  (The in-place call,
+    hebb_out == hebb, takes that two-launch path inside the library; K.plastic_fwd never makes it -
+    test_train_tail_gpu.py::test_plastic_fwd_aliased_trace_output does.)"""
     g = torch.Generator().manual_seed(B * 1000 + N)
     X = rnd(B, N, N, g=g, scale=2.0).to(DEV)
     H = rnd(B, N, N, g=g, scale=0.2).to(DEV)

@@ -17,45 +17,27 @@
 // output transform are fp32 adds/subtracts (no multiplications: the transforms only scale by +-1).
 // The numerics are fp32 arithmetic throughout (tests/test_precision_gpu.py bounds vs fp64).
 //
-// Kernel (one block = 64 tiles x 64 output channels, 4 waves as 2 x 2, each wave a 32 x 32 MFMA
-// tile for all 16 xi: 16 accumulators of 16 fp32 = 256 AGPRs, one wave per SIMD):
-//   * a 16-channel chunk is split into 4 sub-stages, one per row i of B^T (xi = 4i .. 4i+3);
-//   * a sub-stage's LDS slot holds V_xi (4 xi x 3 planes x 64 tiles x 16 channels, bf16) and
-//     U_xi (4 xi x 3 planes x 64 channels x 16), 24 KB each; 2 slots, one barrier per sub-stage;
-//   * thread (tile tt, channel quad q) keeps the 4x4 window of its 4 channels in registers (16
-//     buffer_load_dwordx4, out-of-image pixels fall outside the buffer range and read 0), two
-//     chunks in flight (two register banks), and during sub-stage s forms V of sub-stage s+1 -
-//     8 adds and one exact 3-term split per (xi row, 4 channels) - while the MFMAs of s run;
-//   * U comes pre-split from HBM/L2 by buffer_load ... lds (6 x 1 KB pieces per wave per
-//     sub-stage); 32-byte LDS rows with the 16-byte halves swapped on rows 8..15 mod 16 make
-//     every ds_read_b128 operand read and ds_write_b64 V store conflict-free;
-//   * epilogue: the output transform is lane-local (a lane holds all 16 xi of the same (tile,
-//     4 channels)), then igemm's float4 epilogue (bias, ReLU, residual, masks, concat split,
-//     accumulate) per output pixel; split-K writes pre-bias partial tiles for
-//     igemm_splitk_epilogue_kernel.
+// Kernel: wino4_x6_kernel<FULL, NCB> (below), one work item (tile block x channel block x K
+// split) per block of 4 waves, one wave per SIMD.  An item is 64 tiles x 64 output channels
+// (NCB = 2) or, for short reductions into many channels (wino_wide_items), 32 tiles x 128
+// channels (NCB = 4); FULL selects the general epilogue.  A 16-channel chunk is 4 sub-stages, one
+// per row i of B^T (xi = 4i .. 4i+3); split-K writes pre-bias partial tiles for
+// igemm_splitk_epilogue_kernel.
 #include "conv_common.h"
 
 #ifndef PU_NO_ILV
 #define PU_NO_ILV 0   // 1: leave MFMA / VALU placement to the scheduler (A/B builds)
 #endif
-// wino_x6_kernel ablations (timing only, wrong results): 1 no MFMAs, 2 no V formation (VALU + LDS
-// stores), 3 no window loads, 4 no per-sub-stage barrier (the waits stay), 5 no U DMA, 6 no output
-// stores, 7 no bias loads
-#ifndef PU_WF_ABL
-#define PU_WF_ABL 0
-#endif
-
 
 namespace pu {
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 
-constexpr int WG_BM = 64;                      // tiles per block
-constexpr int WG_BN = 64;                      // output channels per block
-constexpr int WG_HALF = 4 * 3 * 64 * 32;       // bytes of V (or U) in one sub-stage slot
-constexpr int WG_SLOT = 2 * WG_HALF;
+constexpr int WG_BM = 64;                      // tiles per item
+constexpr int WG_BN = 64;                      // output channels per item
+constexpr int WG_WIDE_BM = 32;                 // wide items (wino4_x6_kernel<*, 4>): tiles
+constexpr int WG_WIDE_BN = 128;                //                                      output channels
 
 struct WinoParams {
     IgemmParams p;        // grid (Ho == Hi, Wo == Wi), sources, epilogue, split-K partials
@@ -84,464 +66,18 @@ __device__ __forceinline__ void epi_st4(__amdgpu_buffer_rsrc_t r, unsigned off, 
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, 0);
 }
 
-// One block walks work items (tile block x channel block x K split): PERSIST - one block per CU,
-// each XCD a contiguous range of items, channel block slowest (the items an XCD runs at once share
-// one U slice in its L2); otherwise one item per block (XCD-aware order).
-//
-// The chunks of consecutive items form one stream: the loads a chunk issues for "the next chunk"
-// (its window rows, the first U pieces) target the next item's first chunk at an item's end, so
-// the next item's first sub-stages are in flight during this item's last chunk and epilogue
-// instead of waiting out a cold HBM round trip per item.
-//
-// Sub-stage s (chunk kc, row i): V of s was formed during s-1 (V slots i & 1), U of s was issued
-// three sub-stages earlier (U slots i: a 4-slot ring).  Every load is issued unconditionally
-// (past the last item the buffer range is empty and zeros land), so the wait counts are
-// compile-time exact: issued after U(s) are the window rows of s-3, s-2, s-1 (4 / 4 / 8 / 0 row
-// loads in sub-stages i = 0 / 1 / 2 / 3) and U(s+1), U(s+2) (3 pieces each).
-#ifndef PU_WPP_STAMP
-#define PU_WPP_STAMP 0     // diagnostic build: block 0's per-wave s_memtime before / after every barrier
-#endif
-#if PU_WPP_STAMP
-constexpr int PU_WPP_NSTAMP = 512;
-__device__ unsigned long long pu_wpp_stamp_buf[8 * PU_WPP_NSTAMP];
-// lane 0 of block 0's waves: shader-clock stamp k of wave w (diagnostic builds only; the stamp
-// stores are vector-memory ops and shift the kernel's counted vmcnt waits - timing only)
-__device__ __forceinline__ void wpp_stamp_at(int wave, int& n) {
-    const unsigned long long t = __builtin_amdgcn_s_memtime();
-    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && n < PU_WPP_NSTAMP) pu_wpp_stamp_buf[wave * PU_WPP_NSTAMP + n] = t;
-    ++n;
-}
-#define WPP_STAMP(w, n) wpp_stamp_at(w, n)
-#else
-#define WPP_STAMP(w, n) ((void)0)
-#endif
-template <bool PERSIST>
-__global__ __launch_bounds__(512) void wino_x6_kernel(const WinoParams w) {
-#pragma clang fp contract(off)
-    const IgemmParams& p = w.p;
-    // V slots (VALU-stored) and U slots (LDS-DMA) as separate arrays: the compiler then knows the
-    // V stores / operand reads do not alias the DMA in flight (no vmcnt(0) before LDS accesses)
-    __shared__ __attribute__((aligned(16))) unsigned char ldv0[WG_HALF];
-    __shared__ __attribute__((aligned(16))) unsigned char ldv1[WG_HALF];
-    __shared__ __attribute__((aligned(16))) unsigned char ldu0[WG_HALF];
-    __shared__ __attribute__((aligned(16))) unsigned char ldu1[WG_HALF];
-    __shared__ __attribute__((aligned(16))) unsigned char ldu2[WG_HALF];
-    __shared__ __attribute__((aligned(16))) unsigned char ldu3[WG_HALF];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave & 1, wn = (wave >> 1) & 1, wx = wave >> 2;
-    int nst = 0;
-    const int per_split = w.gm * p.gn;
-    const int total = per_split * p.ksplit;
-
-    // work items of this block: [it, end) with stride step
-    int it, end, step;
-    if (PERSIST) {
-        const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-        const int q8 = total >> 3, r8 = total & 7;
-        const int start = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-        end = start + q8 + (xcd < r8 ? 1 : 0);
-        it = start + local;
-        step = (int)(gridDim.x >> 3);
-    } else {
-        it = xcd_remap(blockIdx.x, gridDim.x);
-        end = it + 1;
-        step = 1;
-    }
-    if (it >= end) return;
-
-    // ---- producer role: tile tt of the block, channels 2q, 2q+1 of each 16-channel chunk.
-    const int tt = tid >> 3, q = tid & 7;
-    const int cs = p.c0;                       // pixel stride (== c1 when c1 != 0)
-    const int shift = p.Wi + 1;                // window corner (2ty-1, 2tx-1) >= (-1, -1)
-    const unsigned pixb = (unsigned)cs * 4u;
-    const float* a0 = p.src0 - (long long)shift * cs;
-    const float* a1 = (p.c1 ? p.src1 : p.src0) - (long long)shift * cs;
-    // V store address of this thread inside a slot (row tt, its 4-byte pair, swizzled half)
-    const int v_st = tt * 32 + (((q >> 2) ^ ((tt >> 3) & 1)) * 16) + (q & 3) * 4;
-
-    // ---- U loader: wave w fills pieces 3w .. 3w+2 (piece P = (j*3 + plane)*2 + row half)
-    const unsigned u_lane = (unsigned)((lane >> 1) * 32 + (((lane & 1) ^ ((lane >> 4) & 1)) * 16));
-    const unsigned u_row = (unsigned)p.N * 32u;                  // bytes per (xi, plane) block
-    unsigned poff[3];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        const int P = wave * 3 + e;
-        poff[e] = (unsigned)(P >> 1) * u_row + (unsigned)((P & 1) * 1024);
-    }
-
-    // ---- MFMA role: positions j = 2wx, 2wx+1 of every row i; operand rows 32*wn + (lane&31)
-    // of U and 32*wm + (lane&31) of V
-    const int rd_sw = (((lane >> 5) ^ ((lane >> 3) & 1)) * 16);
-    const int u_rd = (32 * wn + (lane & 31)) * 32 + rd_sw + 2 * wx * 3 * 2048;
-    const int v_rd = (32 * wm + (lane & 31)) * 32 + rd_sw + 2 * wx * 3 * 2048;
-
-    // an item as the loaders see it: its chunk range, channel block and this thread's window rows
-    struct Item {
-        int kz, m_blk, n_blk, kc0, kc1;
-        unsigned vrow[4];
-        bool c0ok, c3ok, live;
-    };
-    auto decode = [&](int item, Item& I) {
-        I.live = item < end;
-        I.kz = item / per_split;
-        const int rest = item - I.kz * per_split;
-        const int nb = rest / w.gm;          // channel block slowest (U slice shared in L2)
-        I.m_blk = (rest - nb * w.gm) * WG_BM;
-        I.n_blk = nb * WG_BN;
-        I.kc0 = I.kz * w.kc_per;
-        I.kc1 = min(p.C / 16, I.kc0 + w.kc_per);
-        const int m = I.m_blk + tt;
-        int ty = 0, tx = 0, b = 0;
-        const bool mv = I.live && m < w.tiles;
-        if (mv) {
-            const int t2 = fdiv(m, w.dTw);
-            tx = m - t2 * (p.Wo >> 1);
-            b = fdiv(t2, w.dTh);
-            ty = t2 - b * (p.Ho >> 1);
-        }
-        const int y0 = 2 * ty - 1, x0 = 2 * tx - 1;
-        const unsigned base = (unsigned)(((b * p.Hi + y0) * p.Wi + x0 + shift) * cs * 4 + q * 8);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            I.vrow[r] = mv && (unsigned)(y0 + r) < (unsigned)p.Hi ? base + (unsigned)(r * p.Wi * cs * 4) : LEAN_OOB;
-        I.c0ok = x0 >= 0;
-        I.c3ok = x0 + 3 < p.Wi;
-    };
-    Item cur, nxt;
-    decode(it, cur);
-    decode(it + step, nxt);
-
-    typedef float f32x2v __attribute__((ext_vector_type(2)));
-    f32x2v d[16];
-    f32x16 acc[8];                            // [i][jj]
-
-    // window row rr (4 pixels x 2 channels) of chunk kc of item I (zeros past its chunks)
-    auto load_row = [&](const Item& I, int kc, int rr) {
-        if (PU_WF_ABL == 3) {
-#pragma unroll
-            for (int ss = 0; ss < 4; ++ss) d[rr * 4 + ss] = f32x2v{1.f + rr, 0.5f * ss};
-            return;
-        }
-        const int c = kc * 16;
-        const bool second = c >= p.c0;
-        const bool ok = I.live && kc < I.kc1;
-        const __amdgpu_buffer_rsrc_t r = uniform_rsrc(second ? a1 : a0, ok ? w.a_bytes : 0u);
-        const unsigned cb = (unsigned)((second ? c - p.c0 : c) * 4);
-#pragma unroll
-        for (int ss = 0; ss < 4; ++ss) {
-            unsigned vo = I.vrow[rr];
-            if (ss == 0) vo = I.c0ok ? vo : LEAN_OOB;
-            if (ss == 3) vo = I.c3ok ? vo : LEAN_OOB;
-            const unsigned soff = __builtin_amdgcn_readfirstlane(cb + ss * pixb);
-            d[rr * 4 + ss] = __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(r, vo, soff, 0));
-        }
-    };
-    // U pieces of sub-stage (chunk kc, row i) of item I into U slot base (zeros past its chunks)
-    auto load_u = [&](const Item& I, int kc, int i, unsigned char* base) {
-        if (PU_WF_ABL == 5) return;
-        const unsigned bytes = I.live && kc < I.kc1 ? w.u_bytes : 0u;
-        const unsigned sb = (unsigned)((kc * 16 + 4 * i) * 3) * u_row + (unsigned)(I.n_blk * 32);
-#pragma unroll
-        for (int e = 0; e < 3; ++e) lean_load(w.U, bytes, base + (wave * 3 + e) * 1024, u_lane, sb + poff[e]);
-    };
-    // V = row i of B^T d B for this thread's 2 channels -> hi/mid/lo planes in V slot sb
-    auto make_v = [&](auto i_c, unsigned char* sb) {
-        constexpr int i = decltype(i_c)::value;
-        if (PU_WF_ABL == 2) return;
-        f32x2v t[4];
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) {
-            if constexpr (i == 0) t[s2] = d[s2] - d[8 + s2];
-            else if constexpr (i == 1) t[s2] = d[4 + s2] + d[8 + s2];
-            else if constexpr (i == 2) t[s2] = d[8 + s2] - d[4 + s2];
-            else t[s2] = d[4 + s2] - d[12 + s2];
-        }
-        const f32x2v v0 = t[0] - t[2], v1 = t[1] + t[2], v2 = t[2] - t[1], v3 = t[1] - t[3];
-        bf16x8_t h, m, l;
-        split3_pairs(f32x4{v0[0], v0[1], v1[0], v1[1]}, f32x4{v2[0], v2[1], v3[0], v3[1]}, h, m, l);
-        const u32x4 pv[3] = {__builtin_bit_cast(u32x4, h), __builtin_bit_cast(u32x4, m), __builtin_bit_cast(u32x4, l)};
-        unsigned char* base = sb + v_st;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) *reinterpret_cast<unsigned*>(base + (j * 3 + pl) * 2048) = pv[pl][j];
-    };
-    // the 6 MFMAs of position (i, 2wx + jj) from V slot sv / U slot su
-    auto mma = [&](auto x_c, const unsigned char* sv, const unsigned char* su, int jj) {
-        constexpr int x = decltype(x_c)::value;
-        const unsigned char* ub = su + u_rd + jj * 3 * 2048;
-        const unsigned char* vb = sv + v_rd + jj * 3 * 2048;
-        bf16x8_t fu[3], fv[3];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            fu[pl] = *reinterpret_cast<const bf16x8_t*>(ub + pl * 2048);
-            fv[pl] = *reinterpret_cast<const bf16x8_t*>(vb + pl * 2048);
-        }
-        if (PU_WF_ABL == 1) {
-            acc[x][0] += __builtin_bit_cast(float, __builtin_shufflevector(fu[0], fu[1], 0, 1)) +
-                         __builtin_bit_cast(float, __builtin_shufflevector(fu[2], fv[0], 0, 1)) +
-                         __builtin_bit_cast(float, __builtin_shufflevector(fv[1], fv[2], 0, 1));
-            return;
-        }
-        f32x16 c = acc[x];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[1], fv[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[2], fv[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[0], fv[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[1], fv[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[0], fv[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[0], fv[0], c, 0, 0, 0);
-        acc[x] = c;
-    };
-    using I0 = std::integral_constant<int, 0>;
-    auto uslot = [&](int k) -> unsigned char* { return k == 0 ? ldu0 : k == 1 ? ldu1 : k == 2 ? ldu2 : ldu3; };
-
-    // sub-stage (kc, i) of the current item; T / tkc = the stream's next chunk (this item's kc+1,
-    // or the next item's first chunk).  Issues U(s+3) into slot (i+3) & 3 (the slot sub-stage
-    // s-1 read) and the window rows of the next chunk that chunk kc no longer reads (row 0 in
-    // i = 0, row 2 in i = 1, rows 1 and 3 in i = 2).
-    auto sub = [&](int kc, const Item& T, int tkc, auto i_c) {
-        constexpr int i = decltype(i_c)::value;
-        unsigned char* cv = (i & 1) ? ldv1 : ldv0;
-        unsigned char* nv = (i & 1) ? ldv0 : ldv1;
-        unsigned char* cu = uslot(i);
-        unsigned char* fu = uslot((i + 3) & 3);
-        if constexpr (i == 0) asm volatile("s_waitcnt vmcnt(18) lgkmcnt(0)" ::: "memory");
-        else if constexpr (i == 1) asm volatile("s_waitcnt vmcnt(18) lgkmcnt(0)" ::: "memory");
-        else if constexpr (i == 2) asm volatile("s_waitcnt vmcnt(14) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(22) lgkmcnt(0)" ::: "memory");
-        WPP_STAMP(wave, nst);
-        if (PU_WF_ABL != 4) __builtin_amdgcn_s_barrier();
-        WPP_STAMP(wave, nst);
-        asm volatile("" ::: "memory");
-        if constexpr (i == 0) load_u(cur, kc, 3, fu);
-        else load_u(T, tkc, i - 1, fu);
-        asm volatile("" ::: "memory");                  // the wait counts assume U is issued first
-        if constexpr (i == 0) load_row(T, tkc, 0);
-        mma(std::integral_constant<int, 2 * i>{}, cv, cu, 0);
-        if constexpr (i < 3) make_v(std::integral_constant<int, i + 1>{}, nv);
-        else make_v(I0{}, nv);
-        if constexpr (i == 1) load_row(T, tkc, 2);
-        if constexpr (i == 2) {
-            load_row(T, tkc, 1);
-            load_row(T, tkc, 3);
-        }
-        mma(std::integral_constant<int, 2 * i + 1>{}, cv, cu, 1);
-#if !PU_NO_ILV && PU_WF_ABL == 0
-        // Interleave the 12 MFMAs with the V formation (~55 VALU, 12 plane stores): left to
-        // itself the scheduler bunches 6 MFMAs before and 6 after it, and the two waves of a SIMD,
-        // in the same phase between barriers, leave the matrix pipe idle during the VALU
-        __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);        // position 2i operands
-#pragma unroll
-        for (int q = 0; q < 12; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-            if (q == 2) __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);   // position 2i + 1 operands
-        }
-#endif
-    };
-
-    // stream prologue: the first item's whole first window, U of sub-stages 0..2, V of 0
-    load_row(cur, cur.kc0, 0);
-    load_row(cur, cur.kc0, 1);
-    load_row(cur, cur.kc0, 2);
-    load_row(cur, cur.kc0, 3);
-    load_u(cur, cur.kc0, 0, ldu0);
-    load_u(cur, cur.kc0, 1, ldu1);
-    load_u(cur, cur.kc0, 2, ldu2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    make_v(I0{}, ldv0);
-
-    // output-transform exchange through V slot 1 (free at an item boundary: the last sub-stage
-    // read it, the next item's first V is in slot 0), 4 registers per round:
-    // [wm][wn][wx][2][4][64] floats = 16 KB
-    float* xs = reinterpret_cast<float*>(ldv1) + ((wm * 2 + wn) * 2 + wx) * 512;
-    const float* xr = reinterpret_cast<const float*>(ldv1) + ((wm * 2 + wn) * 2 + (1 - wx)) * 512;
-
-    while (true) {
-#pragma unroll
-        for (int x = 0; x < 8; ++x)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[x][r] = 0.f;
-        for (int kc = cur.kc0; kc < cur.kc1; ++kc) {
-            const bool last = kc + 1 >= cur.kc1;
-            const Item& T = last ? nxt : cur;
-            const int tkc = last ? nxt.kc0 : kc + 1;
-            sub(kc, T, tkc, std::integral_constant<int, 0>{});
-            sub(kc, T, tkc, std::integral_constant<int, 1>{});
-            sub(kc, T, tkc, std::integral_constant<int, 2>{});
-            sub(kc, T, tkc, std::integral_constant<int, 3>{});
-        }
-        // every wave is past the last sub-stage's reads of V slot 1 and its V stores are done
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        WPP_STAMP(wave, nst);
-        __builtin_amdgcn_s_barrier();
-        WPP_STAMP(wave, nst);
-        asm volatile("" ::: "memory");
-
-        // ---- output transform Y = A^T M A.  Wave wx holds positions j = 2wx, 2wx+1 of every
-        // row i for its (32 tiles x 32 channels); per element s_py[j] = sum_i A^T[py][i] M[i][j].
-        // Wave wx finishes output row py = wx of the tile: Y[py][0] = (s[0] + s[1]) + s[2],
-        // Y[py][1] = s[1] - (s[2] + s[3]); the partner wave (same wm, wn) supplies the other half.
-        float y0v[16], y1v[16];
-#pragma unroll
-        for (int rd = 0; rd < 4; ++rd) {
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const int r = rd * 4 + r4;
-                float sp[2][2];                          // [py][jj]
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) {
-                    sp[0][jj] = acc[0 * 2 + jj][r] + acc[1 * 2 + jj][r] + acc[2 * 2 + jj][r];
-                    sp[1][jj] = acc[1 * 2 + jj][r] - acc[2 * 2 + jj][r] - acc[3 * 2 + jj][r];
-                }
-                if (wx == 0) {   // j = 0, 1: keeps row 0 as (s0 + s1, s1), sends row 1 likewise
-                    y0v[r] = sp[0][0] + sp[0][1];
-                    y1v[r] = sp[0][1];
-                    xs[r4 * 64 + lane] = sp[1][0] + sp[1][1];
-                    xs[(4 + r4) * 64 + lane] = sp[1][1];
-                } else {         // j = 2, 3: keeps row 1 as (s2, s2 + s3), sends row 0 likewise
-                    y0v[r] = sp[1][0];
-                    y1v[r] = sp[1][0] + sp[1][1];
-                    xs[r4 * 64 + lane] = sp[0][0];
-                    xs[(4 + r4) * 64 + lane] = sp[0][0] + sp[0][1];
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            WPP_STAMP(wave, nst);
-            __builtin_amdgcn_s_barrier();
-            WPP_STAMP(wave, nst);
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const int r = rd * 4 + r4;
-                const float o0 = xr[r4 * 64 + lane], o1 = xr[(4 + r4) * 64 + lane];
-                if (wx == 0) {
-                    y0v[r] = y0v[r] + o0;
-                    y1v[r] = y1v[r] - o1;
-                } else {
-                    y0v[r] = o0 + y0v[r];
-                    y1v[r] = o1 - y1v[r];
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            WPP_STAMP(wave, nst);
-            __builtin_amdgcn_s_barrier();
-            WPP_STAMP(wave, nst);
-            asm volatile("" ::: "memory");
-        }
-        const int e_m = cur.m_blk + 32 * wm + (lane & 31), e_n = cur.n_blk + 32 * wn + 4 * (lane >> 5);
-        const bool e_ok = e_m < w.tiles;
-        const int em = e_ok ? e_m : 0;
-        const int t2 = fdiv(em, w.dTw);
-        const int tx = em - t2 * (p.Wo >> 1);
-        const int b = fdiv(t2, w.dTh);
-        const int ty = t2 - b * (p.Ho >> 1);
-        const long long pix0 = ((long long)b * p.Ho + 2 * ty + wx) * p.Wo + 2 * tx;
-        if (p.ksplit == 1) {
-            // igemm's float4 epilogue (bias, residual, ReLU, mask, channel scale, accumulate) for
-            // the lane's two pixels.  Every operand load is issued, unconditionally and back to
-            // back, before the first store: gfx9's vmcnt counts stores too, so a load issued after
-            // a store (and waited for) waits out that store's round trip - with the loads inside
-            // the per-flag branches each of the 8 stores was followed by a vmcnt(0).  Absent
-            // operands read through an empty buffer range (no memory traffic); lanes past the
-            // last tile load and store out of range.  A 64-channel item lies in one destination
-            // (wino_ok: n0 % 64 == 0), so the destination is item-uniform.
-            const bool first = cur.n_blk < p.n0;
-            const int ld = first ? p.n0 : p.N - p.n0;
-            float* dst = first ? p.dst0 : p.dst1;
-            const float* msk = first ? p.mask0 : p.mask1;
-            const bool relu = p.flags & PU_EPI_RELU, accum = p.flags & PU_EPI_ACCUM;
-            constexpr unsigned FULL = 0x7fffffffu;
-            const __amdgpu_buffer_rsrc_t r_dst = uniform_rsrc(dst, FULL);
-            const __amdgpu_buffer_rsrc_t r_acc = uniform_rsrc(dst, accum ? FULL : 0u);
-            const __amdgpu_buffer_rsrc_t r_res = uniform_rsrc(p.resid, p.resid ? FULL : 0u);
-            const __amdgpu_buffer_rsrc_t r_msk = uniform_rsrc(msk, msk ? FULL : 0u);
-            const __amdgpu_buffer_rsrc_t r_bias = uniform_rsrc(p.bias, p.bias && PU_WF_ABL != 7 ? FULL : 0u);
-            const __amdgpu_buffer_rsrc_t r_cs = uniform_rsrc(p.cscale, p.cscale ? FULL : 0u);
-            const unsigned o_px = e_ok ? (unsigned)(pix0 * ld + e_n - (first ? 0 : p.n0)) * 4u : LEAN_OOB;
-            const unsigned o_row = (unsigned)ld * 4u;
-            const unsigned o_cs = (unsigned)(b * p.cs_ld + e_n) * 4u;
-            f32x4 bv[4], sv[4], rv[4][2], mv[4][2], av[4][2];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bv[g] = epi_ld4(r_bias, (unsigned)(e_n + 8 * g) * 4u);
-                sv[g] = epi_ld4(r_cs, o_cs + 32u * g);
-#pragma unroll
-                for (int o = 0; o < 2; ++o) {
-                    const unsigned off = o_px + o * o_row + 32u * g;
-                    rv[g][o] = epi_ld4(r_res, off);
-                    mv[g][o] = epi_ld4(r_msk, off);
-                    av[g][o] = epi_ld4(r_acc, off);
-                }
-            }
-            // pin every load here, ahead of the stores (the flag branches below would otherwise
-            // take them in, each load then waited for behind the stores before it)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                asm volatile("" :: "v"(bv[g]), "v"(sv[g]));
-#pragma unroll
-                for (int o = 0; o < 2; ++o) asm volatile("" :: "v"(rv[g][o]), "v"(mv[g][o]), "v"(av[g][o]));
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 y[2] = {{y0v[4 * g], y0v[4 * g + 1], y0v[4 * g + 2], y0v[4 * g + 3]},
-                                    {y1v[4 * g], y1v[4 * g + 1], y1v[4 * g + 2], y1v[4 * g + 3]}};
-#pragma unroll
-                for (int o = 0; o < 2; ++o) {
-                    f32x4 v = y[o];
-                    if (p.bias) v += bv[g];
-                    if (p.resid) v += rv[g][o];
-                    if (relu) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                    }
-                    if (msk) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (!(mv[g][o][e] > 0.f)) v[e] = 0.f;
-                    }
-                    if (p.cscale) v *= sv[g];
-                    if (accum) v += av[g][o];
-                    const unsigned off = o_px + o * o_row + 32u * g;
-                    if (PU_WF_ABL == 6) {      // no output stores (timing only): keep v alive
-                        if (v[0] == 1.2345e-30f) epi_st4(r_dst, off, v);
-                    } else {
-                        epi_st4(r_dst, off, v);
-                    }
-                }
-            }
-        } else if (e_ok) {
-            float* part = p.part + (long long)cur.kz * p.M * p.N + pix0 * p.N + e_n;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                *reinterpret_cast<f32x4*>(part + 8 * g) = f32x4{y0v[4 * g], y0v[4 * g + 1], y0v[4 * g + 2], y0v[4 * g + 3]};
-                *reinterpret_cast<f32x4*>(part + p.N + 8 * g) = f32x4{y1v[4 * g], y1v[4 * g + 1], y1v[4 * g + 2], y1v[4 * g + 3]};
-            }
-        }
-        if (!nxt.live) break;
-        it += step;
-        cur = nxt;
-        decode(it + step, nxt);
-    }
-    // the stream's trailing (empty-range) LDS-DMA lands before the block's LDS is released
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
 // ------------------------------------------------------------------ one wave per SIMD: wino4_x6_kernel
-// The same F(2x2,3x3) items (64 tiles x 64 output channels x a K range), products, U / V planes
-// and output-transform expression tree as wino_x6_kernel - bit-identical results - re-tiled for
-// one wave per SIMD: 4 waves, wave j owns position column j of every row i for the WHOLE 64 x 64
-// item (2 x 2 MFMA blocks per position: 4 rows x 4 blocks = 256 accumulators, AGPRs), one item
-// per block.
-// Why: wino_x6_kernel's 8 waves each run a 32 x 32 block per position, so every MFMA needs its
-// own U and V fragment (1 KB of LDS reads per MFMA; 96 KB per sub-stage on top of the 48 KB of U
-// DMA and V stores), and after each sub-stage barrier both waves of a SIMD first wait for their
-// LDS fragment reads.  Here a U fragment feeds 2 MFMAs and a V fragment 2 (24 KB of V reads per
-// sub-stage), U goes straight from L2 into registers one sub-stage ahead (no LDS-DMA), and the
-// sub-stages are software-pipelined so the matrix pipe does not wait for LDS after a barrier:
+// An item is a (tile block x output-channel block x K range) of the F(2x2,3x3) GEMMs.  4 waves,
+// one per SIMD; wave j owns position column j of every row i for the WHOLE item (4 MFMA blocks of
+// 32 x 32 per position - 2 channel x 2 tile blocks, or 4 x 1 for the wide items: 4 rows x 4 blocks
+// = 256 accumulators, AGPRs), one item per block.
+// Why one wave per SIMD: a U fragment feeds 2 MFMAs and a V fragment 2 (24 KB of V reads per
+// sub-stage, where a 32 x 32 block per wave needs a fresh U and V fragment, 1 KB of LDS reads, for
+// every MFMA), U goes straight from L2 into registers ahead of its sub-stage (no LDS staging), and
+// the sub-stages are software-pipelined so the matrix pipe does not wait for LDS after a barrier:
+//   * a V slot holds, per (position, plane), one 32-byte row per tile (16 channels, bf16); the
+//     16-byte halves are swapped on rows 8..15 mod 16, which makes every ds_read_b128 fragment
+//     read and ds_write_b64 V store conflict-free;
 //   * V is formed TWO sub-stages ahead into a 3-slot ring (3 x 24 KB): during sub-stage s the
 //     producer role (thread = tile tt, channel quad qq; its 4x4 window of 4 channels in 16 x f32x4)
 //     forms V(s+2), and every wave pre-reads its 6 fragments of V(s+1) - complete at barrier(s) -
@@ -652,7 +188,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         c3ok = x0 + 3 < p.Wi;
     }
 
-    // ---- MFMA role: V rows 32 tb + (lane & 31) of position j, swizzled half (as wino_x6_kernel)
+    // ---- MFMA role: V rows 32 tb + (lane & 31) of position j, k half lane >> 5 in its swizzled 16 bytes
     const int rd_sw = (((lane >> 5) ^ ((lane >> 3) & 1)) * 16);
     const int v_rd = (lane & 31) * 32 + rd_sw + wj * 3 * PS;
     // U fragment (n = 32 cb + (lane & 31), k half lane >> 5) of (chunk, xi, plane): 1 KB per wave
@@ -756,7 +292,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
     };
     // the 24 MFMAs of position (i, wj): U slot su x V slot sv, the 6 products of each of the
-    // 4 blocks in wino_x6_kernel's order; the item's first chunk starts from C = 0
+    // 4 blocks smallest terms first (mid x mid, lo x hi, hi x lo, mid x hi, hi x mid, hi x hi - the
+    // order the results are pinned to); the item's first chunk starts from C = 0
     auto mma = [&](auto i_c, auto su_c, auto sl_c, auto first_c) {
         constexpr int i = decltype(i_c)::value;
         constexpr int su = decltype(su_c)::value;     // U slot
@@ -903,7 +440,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     asm volatile("" ::: "memory");
     W4S(2);
 
-    // ---- output transform.  Column sums s_py[j] (lane-local, wino_x6_kernel's order):
+    // ---- output transform.  Column sums s_py[j] (lane-local, summed in this order):
     // s_0 = (M0 + M1) + M2, s_1 = (M1 - M2) - M3.  Wave b owns block b = (cb, tb) = (b >> 1,
     // b & 1); in round r wave j sends block (j + r) & 3 and receives block b from wave (b - r) & 3.
     // Specialised per wave (a uniform switch) so every register index is static; the column sums
@@ -1033,8 +570,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         return f32x4{a3[4 * g], a3[4 * g + 1], a3[4 * g + 2], a3[4 * g + 3]};
     };
     if (p.ksplit == 1) {
-        // wino_x6_kernel's batched float4 epilogue for both output rows: operand loads first,
-        // then the stores
+        // igemm's float4 epilogue (bias, residual, ReLU, mask, channel scale, accumulate), batched:
+        // every operand load of an output row is issued, unconditionally and back to back, before
+        // the row's first store.  gfx9's vmcnt counts stores too, so a load issued after a store
+        // (and waited for) waits out that store's round trip.  Absent operands read through an
+        // empty buffer range (no memory traffic); lanes past the last tile load and store out of
+        // range.
         const bool first = n_blk + 32 * cbo < p.n0;     // a 32-channel block lies in one destination
         const int ld = first ? p.n0 : p.N - p.n0;
         float* dst = first ? p.dst0 : p.dst1;
@@ -1144,387 +685,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     W4S(4);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     W4S(5);
-}
-
-// ------------------------------------------------------------------ 128-channel Winograd items
-// wino128_x6_kernel: the same F(2x2,3x3) arithmetic, products and output transform as
-// wino_x6_kernel, with items of 32 tiles x 128 output channels instead of 64 x 64, so each V
-// element formed feeds 128 outputs instead of 64 (half the formation work per MFMA; a layer's V is
-// formed once per 128 channels) at the price of twice the U bytes per MFMA (a 48 KB U slice per
-// sub-stage).  8 waves (wn, wx): 32 tiles x 32 channels (32 wn ..) x the 8 positions of j = 2wx,
-// 2wx+1 - 128 accumulators, as in wino_x6_kernel.  Thread (tile tt, channel q) holds the 4x4
-// window of one channel and forms its V row per sub-stage (4 values, exact 3-term split, 12
-// 2-byte plane stores).  LDS: V 2 x 12 KB, U 2 x 48 KB (U issued one sub-stage ahead; the slice is
-// L2-resident - every item of an XCD shares it, channel block slowest), 120 KB.
-#ifndef PU_W2_ABL
-#define PU_W2_ABL 0     // wino128_x6_kernel ablations (timing only, wrong results): 1 no U DMA, 2 no V formation
-#endif
-constexpr int W2_BM = 32;
-constexpr int W2_BN = 128;
-constexpr int W2_VH = 4 * 3 * W2_BM * 32;      // 12 KB
-constexpr int W2_UH = 4 * 3 * W2_BN * 32;      // 48 KB
-
-__device__ __forceinline__ void split3_quad(const f32x4 x, bf16x4_t& h, bf16x4_t& m, bf16x4_t& l) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const __bf16 a = (__bf16)x[e];
-        const float r = x[e] - (float)a;
-        const __bf16 b = (__bf16)r;
-        h[e] = a;
-        m[e] = b;
-        l[e] = (__bf16)(r - (float)b);
-    }
-}
-
-template <bool PERSIST>
-__global__ __launch_bounds__(512) void wino128_x6_kernel(const WinoParams w) {
-#pragma clang fp contract(off)
-    const IgemmParams& p = w.p;
-    __shared__ __attribute__((aligned(16))) unsigned char ldv0[W2_VH];
-    __shared__ __attribute__((aligned(16))) unsigned char ldv1[W2_VH];
-    __shared__ __attribute__((aligned(16))) unsigned char ldu0[W2_UH];
-    __shared__ __attribute__((aligned(16))) unsigned char ldu1[W2_UH];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wn = wave & 3, wx = wave >> 2;
-    const int per_split = w.gm * p.gn;
-    const int total = per_split * p.ksplit;
-
-    int it, end, step;
-    if (PERSIST) {
-        const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-        const int q8 = total >> 3, r8 = total & 7;
-        const int start = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-        end = start + q8 + (xcd < r8 ? 1 : 0);
-        it = start + local;
-        step = (int)(gridDim.x >> 3);
-    } else {
-        it = xcd_remap(blockIdx.x, gridDim.x);
-        end = it + 1;
-        step = 1;
-    }
-    if (it >= end) return;
-
-    // ---- producer role: tile tt of the item, channel q of each 16-channel chunk
-    const int tt = tid >> 4, q = tid & 15;
-    const int cs = p.c0;
-    const int shift = p.Wi + 1;
-    const unsigned pixb = (unsigned)cs * 4u;
-    const float* a0 = p.src0 - (long long)shift * cs;
-    const float* a1 = (p.c1 ? p.src1 : p.src0) - (long long)shift * cs;
-    const int v_st = tt * 32 + (((q >> 3) ^ ((tt >> 3) & 1)) * 16) + (q & 7) * 2;
-
-    // ---- U loader: wave w fills pieces 6w .. 6w+5 (piece P = (j*3 + plane)*4 + row quarter)
-    const unsigned u_lane = (unsigned)((lane >> 1) * 32 + (((lane & 1) ^ ((lane >> 4) & 1)) * 16));
-    const unsigned u_row = (unsigned)p.N * 32u;
-    unsigned poff[6];
-#pragma unroll
-    for (int e = 0; e < 6; ++e) {
-        const int P = wave * 6 + e;
-        poff[e] = (unsigned)(P >> 2) * u_row + (unsigned)((P & 3) * 1024);
-    }
-
-    // ---- MFMA role: positions j = 2wx, 2wx+1; U rows 32*wn + (lane&31), V rows lane&31
-    const int rd_sw = (((lane >> 5) ^ ((lane >> 3) & 1)) * 16);
-    const int u_rd = (32 * wn + (lane & 31)) * 32 + rd_sw + 2 * wx * 3 * 4096;
-    const int v_rd = (lane & 31) * 32 + rd_sw + 2 * wx * 3 * 1024;
-
-    struct Item {
-        int kz, m_blk, n_blk, kc0, kc1;
-        unsigned vrow[4];
-        bool c0ok, c3ok, live;
-    };
-    auto decode = [&](int item, Item& I) {
-        I.live = item < end;
-        I.kz = item / per_split;
-        const int rest = item - I.kz * per_split;
-        const int nb = rest / w.gm;
-        I.m_blk = (rest - nb * w.gm) * W2_BM;
-        I.n_blk = nb * W2_BN;
-        I.kc0 = I.kz * w.kc_per;
-        I.kc1 = min(p.C / 16, I.kc0 + w.kc_per);
-        const int m = I.m_blk + tt;
-        int ty = 0, tx = 0, b = 0;
-        const bool mv = I.live && m < w.tiles;
-        if (mv) {
-            const int t2 = fdiv(m, w.dTw);
-            tx = m - t2 * (p.Wo >> 1);
-            b = fdiv(t2, w.dTh);
-            ty = t2 - b * (p.Ho >> 1);
-        }
-        const int y0 = 2 * ty - 1, x0 = 2 * tx - 1;
-        const unsigned base = (unsigned)(((b * p.Hi + y0) * p.Wi + x0 + shift) * cs * 4 + q * 4);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            I.vrow[r] = mv && (unsigned)(y0 + r) < (unsigned)p.Hi ? base + (unsigned)(r * p.Wi * cs * 4) : LEAN_OOB;
-        I.c0ok = x0 >= 0;
-        I.c3ok = x0 + 3 < p.Wi;
-    };
-    Item cur, nxt;
-    decode(it, cur);
-    decode(it + step, nxt);
-
-    float d[16];
-    f32x16 acc[8];
-
-    auto load_row = [&](const Item& I, int kc, int rr) {
-        const int c = kc * 16;
-        const bool second = c >= p.c0;
-        const bool ok = I.live && kc < I.kc1;
-        const __amdgpu_buffer_rsrc_t r = uniform_rsrc(second ? a1 : a0, ok ? w.a_bytes : 0u);
-        const unsigned cb = (unsigned)((second ? c - p.c0 : c) * 4);
-#pragma unroll
-        for (int ss = 0; ss < 4; ++ss) {
-            unsigned vo = I.vrow[rr];
-            if (ss == 0) vo = I.c0ok ? vo : LEAN_OOB;
-            if (ss == 3) vo = I.c3ok ? vo : LEAN_OOB;
-            const unsigned soff = __builtin_amdgcn_readfirstlane(cb + ss * pixb);
-            d[rr * 4 + ss] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, soff, 0));
-        }
-    };
-    auto load_u = [&](const Item& I, int kc, int i, unsigned char* base) {
-        if (PU_W2_ABL == 1) return;
-        const unsigned bytes = I.live && kc < I.kc1 ? w.u_bytes : 0u;
-        const unsigned sb = (unsigned)((kc * 16 + 4 * i) * 3) * u_row + (unsigned)(I.n_blk * 32);
-#pragma unroll
-        for (int e = 0; e < 6; ++e) lean_load(w.U, bytes, base + (wave * 6 + e) * 1024, u_lane, sb + poff[e]);
-    };
-    // V = row i of B^T d B for this thread's channel -> hi/mid/lo planes in V slot sb
-    auto make_v = [&](auto i_c, unsigned char* sb) {
-        constexpr int i = decltype(i_c)::value;
-        if (PU_W2_ABL == 2) return;
-        float t[4];
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) {
-            if constexpr (i == 0) t[s2] = d[s2] - d[8 + s2];
-            else if constexpr (i == 1) t[s2] = d[4 + s2] + d[8 + s2];
-            else if constexpr (i == 2) t[s2] = d[8 + s2] - d[4 + s2];
-            else t[s2] = d[4 + s2] - d[12 + s2];
-        }
-        const f32x4 v = {t[0] - t[2], t[1] + t[2], t[2] - t[1], t[1] - t[3]};
-        bf16x4_t h, m, l;
-        split3_quad(v, h, m, l);
-        unsigned char* base = sb + v_st;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            *reinterpret_cast<__bf16*>(base + (j * 3 + 0) * 1024) = h[j];
-            *reinterpret_cast<__bf16*>(base + (j * 3 + 1) * 1024) = m[j];
-            *reinterpret_cast<__bf16*>(base + (j * 3 + 2) * 1024) = l[j];
-        }
-    };
-    auto mma = [&](auto x_c, const unsigned char* sv, const unsigned char* su, int jj) {
-        constexpr int x = decltype(x_c)::value;
-        const unsigned char* ub = su + u_rd + jj * 3 * 4096;
-        const unsigned char* vb = sv + v_rd + jj * 3 * 1024;
-        bf16x8_t fu[3], fv[3];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            fu[pl] = *reinterpret_cast<const bf16x8_t*>(ub + pl * 4096);
-            fv[pl] = *reinterpret_cast<const bf16x8_t*>(vb + pl * 1024);
-        }
-        f32x16 c = acc[x];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[1], fv[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[2], fv[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[0], fv[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[1], fv[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[0], fv[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fu[0], fv[0], c, 0, 0, 0);
-        acc[x] = c;
-    };
-    using I0 = std::integral_constant<int, 0>;
-
-    // sub-stage (kc, i): V slot i & 1 (formed during the previous sub-stage), U slot i & 1 (issued
-    // during the previous sub-stage).  Issues U of the stream's next sub-stage into the other slot
-    // (read by the previous sub-stage, which every wave has left at the barrier) and the window
-    // rows of the next chunk that this chunk no longer reads (row 0 in i = 0, row 2 in i = 1, rows
-    // 1 and 3 in i = 2).  Wait counts: the rows issued after U in the previous sub-stage.
-    auto sub = [&](int kc, const Item& T, int tkc, auto i_c) {
-        constexpr int i = decltype(i_c)::value;
-        unsigned char* cv = (i & 1) ? ldv1 : ldv0;
-        unsigned char* nv = (i & 1) ? ldv0 : ldv1;
-        unsigned char* cu = (i & 1) ? ldu1 : ldu0;
-        unsigned char* fu = (i & 1) ? ldu0 : ldu1;
-        if constexpr (i == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        else if constexpr (i == 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        else if constexpr (i == 2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if constexpr (i < 3) load_u(cur, kc, i + 1, fu);
-        else load_u(T, tkc, 0, fu);
-        asm volatile("" ::: "memory");                  // the wait counts assume U is issued first
-        if constexpr (i == 0) load_row(T, tkc, 0);
-        mma(std::integral_constant<int, 2 * i>{}, cv, cu, 0);
-        if constexpr (i < 3) make_v(std::integral_constant<int, i + 1>{}, nv);
-        else make_v(I0{}, nv);
-        if constexpr (i == 1) load_row(T, tkc, 2);
-        if constexpr (i == 2) {
-            load_row(T, tkc, 1);
-            load_row(T, tkc, 3);
-        }
-        mma(std::integral_constant<int, 2 * i + 1>{}, cv, cu, 1);
-    };
-
-    // stream prologue: the first item's whole first window and U of its sub-stage 0, V of 0
-    load_row(cur, cur.kc0, 0);
-    load_row(cur, cur.kc0, 1);
-    load_row(cur, cur.kc0, 2);
-    load_row(cur, cur.kc0, 3);
-    load_u(cur, cur.kc0, 0, ldu0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    make_v(I0{}, ldv0);
-
-    // output-transform exchange through U slot 1 (free at an item boundary: the last sub-stage
-    // read it; the next item's U(0) is in slot 0): [wn][wx][2][4][64] floats = 16 KB per round
-    float* xs = reinterpret_cast<float*>(ldu1) + (wn * 2 + wx) * 512;
-    const float* xr = reinterpret_cast<const float*>(ldu1) + (wn * 2 + (1 - wx)) * 512;
-
-    while (true) {
-#pragma unroll
-        for (int x = 0; x < 8; ++x)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[x][r] = 0.f;
-        for (int kc = cur.kc0; kc < cur.kc1; ++kc) {
-            const bool last = kc + 1 >= cur.kc1;
-            const Item& T = last ? nxt : cur;
-            const int tkc = last ? nxt.kc0 : kc + 1;
-            sub(kc, T, tkc, std::integral_constant<int, 0>{});
-            sub(kc, T, tkc, std::integral_constant<int, 1>{});
-            sub(kc, T, tkc, std::integral_constant<int, 2>{});
-            sub(kc, T, tkc, std::integral_constant<int, 3>{});
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-
-        // output transform, as wino_x6_kernel (wave wx finishes output row py = wx of the tile)
-        float y0v[16], y1v[16];
-#pragma unroll
-        for (int rd = 0; rd < 4; ++rd) {
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const int r = rd * 4 + r4;
-                float sp[2][2];
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) {
-                    sp[0][jj] = acc[0 * 2 + jj][r] + acc[1 * 2 + jj][r] + acc[2 * 2 + jj][r];
-                    sp[1][jj] = acc[1 * 2 + jj][r] - acc[2 * 2 + jj][r] - acc[3 * 2 + jj][r];
-                }
-                if (wx == 0) {
-                    y0v[r] = sp[0][0] + sp[0][1];
-                    y1v[r] = sp[0][1];
-                    xs[r4 * 64 + lane] = sp[1][0] + sp[1][1];
-                    xs[(4 + r4) * 64 + lane] = sp[1][1];
-                } else {
-                    y0v[r] = sp[1][0];
-                    y1v[r] = sp[1][0] + sp[1][1];
-                    xs[r4 * 64 + lane] = sp[0][0];
-                    xs[(4 + r4) * 64 + lane] = sp[0][0] + sp[0][1];
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const int r = rd * 4 + r4;
-                const float o0 = xr[r4 * 64 + lane], o1 = xr[(4 + r4) * 64 + lane];
-                if (wx == 0) {
-                    y0v[r] = y0v[r] + o0;
-                    y1v[r] = y1v[r] - o1;
-                } else {
-                    y0v[r] = o0 + y0v[r];
-                    y1v[r] = o1 - y1v[r];
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
-        const int e_m = cur.m_blk + (lane & 31), e_n = cur.n_blk + 32 * wn + 4 * (lane >> 5);
-        const bool e_ok = e_m < w.tiles;
-        const int em = e_ok ? e_m : 0;
-        const int t2 = fdiv(em, w.dTw);
-        const int tx = em - t2 * (p.Wo >> 1);
-        const int b = fdiv(t2, w.dTh);
-        const int ty = t2 - b * (p.Ho >> 1);
-        const long long pix0 = ((long long)b * p.Ho + 2 * ty + wx) * p.Wo + 2 * tx;
-        if (p.ksplit == 1) {
-            // the batched float4 epilogue of wino_x6_kernel; a wave's 32 channels lie in one
-            // destination (n0 % 32 == 0, host)
-            const bool first = cur.n_blk + 32 * wn < p.n0;
-            const int ld = first ? p.n0 : p.N - p.n0;
-            float* dst = first ? p.dst0 : p.dst1;
-            const float* msk = first ? p.mask0 : p.mask1;
-            const bool relu = p.flags & PU_EPI_RELU, accum = p.flags & PU_EPI_ACCUM;
-            constexpr unsigned FULL = 0x7fffffffu;
-            const __amdgpu_buffer_rsrc_t r_dst = uniform_rsrc(dst, FULL);
-            const __amdgpu_buffer_rsrc_t r_acc = uniform_rsrc(dst, accum ? FULL : 0u);
-            const __amdgpu_buffer_rsrc_t r_res = uniform_rsrc(p.resid, p.resid ? FULL : 0u);
-            const __amdgpu_buffer_rsrc_t r_msk = uniform_rsrc(msk, msk ? FULL : 0u);
-            const __amdgpu_buffer_rsrc_t r_bias = uniform_rsrc(p.bias, p.bias ? FULL : 0u);
-            const __amdgpu_buffer_rsrc_t r_cs = uniform_rsrc(p.cscale, p.cscale ? FULL : 0u);
-            const unsigned o_px = e_ok ? (unsigned)(pix0 * ld + e_n - (first ? 0 : p.n0)) * 4u : LEAN_OOB;
-            const unsigned o_row = (unsigned)ld * 4u;
-            const unsigned o_cs = (unsigned)(b * p.cs_ld + e_n) * 4u;
-            f32x4 bv[4], sv[4], rv[4][2], mv[4][2], av[4][2];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bv[g] = epi_ld4(r_bias, (unsigned)(e_n + 8 * g) * 4u);
-                sv[g] = epi_ld4(r_cs, o_cs + 32u * g);
-#pragma unroll
-                for (int o = 0; o < 2; ++o) {
-                    const unsigned off = o_px + o * o_row + 32u * g;
-                    rv[g][o] = epi_ld4(r_res, off);
-                    mv[g][o] = epi_ld4(r_msk, off);
-                    av[g][o] = epi_ld4(r_acc, off);
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                asm volatile("" :: "v"(bv[g]), "v"(sv[g]));
-#pragma unroll
-                for (int o = 0; o < 2; ++o) asm volatile("" :: "v"(rv[g][o]), "v"(mv[g][o]), "v"(av[g][o]));
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 y[2] = {{y0v[4 * g], y0v[4 * g + 1], y0v[4 * g + 2], y0v[4 * g + 3]},
-                                    {y1v[4 * g], y1v[4 * g + 1], y1v[4 * g + 2], y1v[4 * g + 3]}};
-#pragma unroll
-                for (int o = 0; o < 2; ++o) {
-                    f32x4 v = y[o];
-                    if (p.bias) v += bv[g];
-                    if (p.resid) v += rv[g][o];
-                    if (relu) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                    }
-                    if (msk) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (!(mv[g][o][e] > 0.f)) v[e] = 0.f;
-                    }
-                    if (p.cscale) v *= sv[g];
-                    if (accum) v += av[g][o];
-                    epi_st4(r_dst, o_px + o * o_row + 32u * g, v);
-                }
-            }
-        } else if (e_ok) {
-            float* part = p.part + (long long)cur.kz * p.M * p.N + pix0 * p.N + e_n;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                *reinterpret_cast<f32x4*>(part + 8 * g) = f32x4{y0v[4 * g], y0v[4 * g + 1], y0v[4 * g + 2], y0v[4 * g + 3]};
-                *reinterpret_cast<f32x4*>(part + p.N + 8 * g) = f32x4{y1v[4 * g], y1v[4 * g + 1], y1v[4 * g + 2], y1v[4 * g + 3]};
-            }
-        }
-        if (!nxt.live) break;
-        it += step;
-        cur = nxt;
-        decode(it + step, nxt);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // U = G g G^T per (n, 8 consecutive c), fp64 then rounded to fp32 and split into hi/mid/lo bf16:
@@ -1640,31 +800,23 @@ __global__ __launch_bounds__(256) void wino_pack_kernel(const WinoPackBatch bt) 
 
 // host side -------------------------------------------------------------------------------------
 
+// Wide items (32 tiles x 128 output channels, wino4_x6_kernel<*, 4>) instead of 64 x 64.  The gate
+// matches ANY qualifying conv with a short reduction (C < 128) into more than 64 output channels
+// that come in whole 128-channel items, each 32-channel block of an item in one destination:
+// forward layers such as 64 -> 128 as well as the concat layers' data gradients (64 -> 128 / 256)
+// it was measured on (top 0.426 -> 0.409 ms, l2 0.200 -> 0.195 against the direct kernel,
+// profiles/r06_experiments/wino4_ab.txt).  With 64 x 64 items such a layer re-forms the same V
+// once per 64-channel block for little MFMA work; a wide item forms it once per 128 channels.
+// punet/kernels.py's wino_wanted mirrors this rule when it decides which layers get a packed U.
+static bool wino_wide_items(const pu_conv_args* a) {
+    const int C = a->c0 + a->c1;
+    return C < 128 && a->n > WG_BN && a->n % WG_WIDE_BN == 0 && (a->n0 == a->n || a->n0 % 32 == 0);
+}
+
 // the layers the Winograd kernel takes (the caller passed U): 3x3 / s1 / p1, same-size even grid,
 // 16-channel chunks from one source each with one pixel stride (c1 == 0 or c1 == c0), an even
 // number of chunks, 64-channel output blocks, the float4 epilogue, no ConvT shuffle, buffers
 // addressable with 32-bit offsets
-// 128-channel items (wino128_x6_kernel) for layers with n % 128 == 0: opt-in, PU_WINO128=1 - they
-// measured slower than the 64 x 64 items on every C2 layer (profiles/r05_experiments/wino128_ab.txt)
-static bool wino128_on() {
-    static const bool on = [] {
-        const char* e = getenv("PU_WINO128");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-
-static bool wino4_on();
-// 32-tile x 128-channel items: the 8-wave wino128_x6_kernel (PU_WINO128=1 with PU_WINO4=0), or the
-// one-wave-per-SIMD kernel's wide items (PU_WINO4_WIDE=1)
-static int wino4_wide_mode();
-static bool wino128_use(const pu_conv_args* a) {
-    const int C = a->c0 + a->c1;
-    const int wm = wino4_wide_mode();
-    const bool on = wino4_on() ? (wm == 1 || (wm == 2 && C < 128 && a->n > WG_BN)) : wino128_on();
-    return on && a->n % W2_BN == 0 && (a->n0 == a->n || a->n0 % 32 == 0);
-}
-
 bool wino_ok(const pu_conv_args* a, bool vec_epi) {
     const int C = a->c0 + a->c1;
     if (!a->wino || !a->weight6) return false;
@@ -1672,17 +824,16 @@ bool wino_ok(const pu_conv_args* a, bool vec_epi) {
     if (a->in_h != a->out_h || a->in_w != a->out_w || (a->out_h & 1) || (a->out_w & 1)) return false;
     if (a->c0 % 16 || (a->c1 != 0 && a->c1 != a->c0) || C % 32) return false;
     if (a->n % WG_BN || !vec_epi || (a->flags & PU_EPI_SHUFFLE2)) return false;
-    // a short reduction (4 chunks) over several 64-channel output blocks re-forms the same V once
-    // per block for little MFMA work: the concat layers' data gradients (64 -> 128 / 256) stay
-    // on the direct kernel (measured: top_cat dgrad 0.43 vs 0.41 ms, l2_cat 0.21 vs 0.20)
-    if (C < 128 && a->n > WG_BN && !wino128_use(a)) return false;
+    // a short reduction into several 64-channel blocks runs as wide items or, where those do not
+    // fit (n % 128, a split column off the 32-channel blocks), stays on the direct kernel
+    if (C < 128 && a->n > WG_BN && !wino_wide_items(a)) return false;
     const long long px = (long long)a->batch * a->in_h * a->in_w + a->in_w + 1;
     if (px * a->c0 * 4 >= (1LL << 31)) return false;
     if ((long long)C * a->n * 96 >= (1LL << 31)) return false;
-    // the epilogue's 32-bit destination offsets and item-uniform destination (64-channel items
-    // never straddle the split column n0)
+    // the epilogue's 32-bit destination offsets and one destination per wave (64-channel items
+    // never straddle the split column n0; a wide item's 32-channel blocks never do)
     if ((long long)a->batch * a->out_h * a->out_w * a->n * 4 >= (1LL << 31) - 64) return false;
-    if (a->n0 != a->n && a->n0 % (wino128_use(a) ? 32 : WG_BN)) return false;
+    if (a->n0 != a->n && a->n0 % (wino_wide_items(a) ? 32 : WG_BN)) return false;
     return ((uintptr_t)a->wino & 15) == 0;
 }
 
@@ -1691,8 +842,8 @@ bool wino_ok(const pu_conv_args* a, bool vec_epi) {
 void wino_plan(const pu_conv_args* a, int* ksplit, int* kc_per) {
     const int C = a->c0 + a->c1;
     const long long tiles = (long long)a->batch * (a->out_h / 2) * (a->out_w / 2);
-    const bool w128 = wino128_use(a);
-    const int blocks = ceil_div(tiles, w128 ? W2_BM : WG_BM) * (a->n / (w128 ? W2_BN : WG_BN));
+    const bool wide = wino_wide_items(a);
+    const int blocks = ceil_div(tiles, wide ? WG_WIDE_BM : WG_BM) * (a->n / (wide ? WG_WIDE_BN : WG_BN));
     const int chunks = C / 16;
     *ksplit = 1;
     *kc_per = chunks;
@@ -1706,46 +857,14 @@ void wino_plan(const pu_conv_args* a, int* ksplit, int* kc_per) {
     *ksplit = ceil_div(chunks, per);
 }
 
-// persistent blocks (default) or one block per item: PU_WINO_PERSIST=0 (A/B runs)
-static bool wino_persist() {
-    static const bool on = [] {
-        const char* e = getenv("PU_WINO_PERSIST");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// 64 x 64 items on one wave per SIMD (wino4_x6_kernel, bit-identical to wino_x6_kernel; default):
-// PU_WINO4=0 keeps the 8-wave kernel (A/B runs, profiles/r06_experiments/wino4_ab.txt)
-static bool wino4_on() {
-    static const bool on = [] {
-        const char* e = getenv("PU_WINO4");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// the one-wave-per-SIMD kernel's 32-tile x 128-channel items: PU_WINO4_WIDE=1 for every layer with
-// n % 128 == 0 (bit-identical, measured no faster than the 64 x 64 items,
-// profiles/r06_experiments/wino4_ab.txt); =2 (default) only for the short reductions (C < 128)
-// into several 64-channel blocks, which the 64 x 64 items leave to the direct kernel (the concat
-// data gradients: top 0.426 -> 0.409 ms, l2 0.200 -> 0.195); =0 none
-static int wino4_wide_mode() {
-    static const int m = [] {
-        const char* e = getenv("PU_WINO4_WIDE");
-        return !e ? 2 : e[0] == '1' ? 1 : e[0] == '2' ? 2 : 0;
-    }();
-    return m;
-}
-
 int wino_launch(const pu_conv_args* a, IgemmParams p, hipStream_t s) {
     WinoParams w;
     w.p = p;
     w.U = reinterpret_cast<const __bf16*>(a->wino);
     w.tiles = a->batch * (a->out_h / 2) * (a->out_w / 2);
-    const bool w128 = wino128_use(a);
-    w.gm = ceil_div(w.tiles, w128 ? W2_BM : WG_BM);
-    w.p.gn = a->n / (w128 ? W2_BN : WG_BN);
+    const bool wide = wino_wide_items(a);
+    w.gm = ceil_div(w.tiles, wide ? WG_WIDE_BM : WG_BM);
+    w.p.gn = a->n / (wide ? WG_WIDE_BN : WG_BN);
     w.dTw = make_fastdiv(a->out_w / 2);
     w.dTh = make_fastdiv(a->out_h / 2);
     w.a_bytes = (unsigned)(((long long)a->batch * a->in_h * a->in_w + a->in_w + 1) * a->c0 * 4);
@@ -1760,34 +879,20 @@ int wino_launch(const pu_conv_args* a, IgemmParams p, hipStream_t s) {
     w.p.part = (float*)a->workspace;
     w.kc_per = per;
     const int items = w.gm * w.p.gn * ks;
-    if (w128 && !wino4_on()) {
-        if (wino_persist() && items > 256)
-            hipLaunchKernelGGL(wino128_x6_kernel<true>, dim3(256), dim3(512), 0, s, w);
-        else
-            hipLaunchKernelGGL(wino128_x6_kernel<false>, dim3((unsigned)items), dim3(512), 0, s, w);
-        return ks;
+    // one item per block (the pipelined kernel keeps the next chunks' rows in flight per item)
+    const bool full = p.resid || p.cscale || (p.flags & PU_EPI_ACCUM);
+    const dim3 g((unsigned)items);
+    if (wide) {
+        if (full) hipLaunchKernelGGL((wino4_x6_kernel<true, 4>), g, dim3(256), 0, s, w);
+        else hipLaunchKernelGGL((wino4_x6_kernel<false, 4>), g, dim3(256), 0, s, w);
+    } else {
+        if (full) hipLaunchKernelGGL((wino4_x6_kernel<true, 2>), g, dim3(256), 0, s, w);
+        else hipLaunchKernelGGL((wino4_x6_kernel<false, 2>), g, dim3(256), 0, s, w);
     }
-    if (wino4_on()) {
-        // one item per block (the pipelined kernel keeps the next chunks' rows in flight per item)
-        const bool full = p.resid || p.cscale || (p.flags & PU_EPI_ACCUM);
-        const dim3 g((unsigned)items);
-        if (w128) {
-            if (full) hipLaunchKernelGGL((wino4_x6_kernel<true, 4>), g, dim3(256), 0, s, w);
-            else hipLaunchKernelGGL((wino4_x6_kernel<false, 4>), g, dim3(256), 0, s, w);
-        } else {
-            if (full) hipLaunchKernelGGL((wino4_x6_kernel<true, 2>), g, dim3(256), 0, s, w);
-            else hipLaunchKernelGGL((wino4_x6_kernel<false, 2>), g, dim3(256), 0, s, w);
-        }
-        return ks;
-    }
-    if (wino_persist() && items > 256)
-        hipLaunchKernelGGL(wino_x6_kernel<true>, dim3(256), dim3(512), 0, s, w);
-    else
-        hipLaunchKernelGGL(wino_x6_kernel<false>, dim3((unsigned)items), dim3(512), 0, s, w);
     return ks;
 }
 
-int wino_item_channels(const pu_conv_args* a) { return wino128_use(a) ? W2_BN : WG_BN; }
+int wino_item_channels(const pu_conv_args* a) { return wino_wide_items(a) ? WG_WIDE_BN : WG_BN; }
 
 size_t wino_workspace_bytes(const pu_conv_args* a) {
     int ks, per;
@@ -1798,15 +903,6 @@ size_t wino_workspace_bytes(const pu_conv_args* a) {
 }  // namespace pu
 
 using namespace pu;
-
-#if PU_WPP_STAMP
-// diagnostic build only: copy block 0's barrier stamps ([8 waves][PU_WPP_NSTAMP] shader cycles)
-extern "C" int pu_wpp_stamps(unsigned long long* dst, int n) {
-    if (n > 8 * PU_WPP_NSTAMP) n = 8 * PU_WPP_NSTAMP;
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(pu_wpp_stamp_buf), (size_t)n * 8, 0, hipMemcpyDeviceToHost) == hipSuccess
-               ? n : -1;
-}
-#endif
 
 #if PU_W4_ITEM_STAMP
 // diagnostic build only: per-block item stamps of the last wino4 launch ([block][8]: entry,

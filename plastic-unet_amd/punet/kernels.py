@@ -83,14 +83,6 @@ def set_wino(on):
     return prev
 
 
-# 32-tile x 128-channel Winograd items (csrc/winograd.hip wino128_use reads the same variables once
-# per process): the one-wave-per-SIMD kernel's wide items (PU_WINO4_WIDE=1 everywhere, =2 - the
-# default - for the short reductions only, =0 none), or with PU_WINO4=0 the 8-wave PU_WINO128=1 kernel
-_WINO4 = os.environ.get("PU_WINO4", "1") != "0"
-_WINO128 = os.environ.get("PU_WINO4_WIDE", "2") in ("1", "2") if _WINO4 else \
-    os.environ.get("PU_WINO128", "0") == "1"
-
-
 def wino_wanted(w, mode):
     """Whether a packed conv operand of parameter w (OIHW 3x3) should carry a Winograd operand:
     the reduced channel count a multiple of 32 and the produced one of 64 (the kernel's chunks
@@ -98,8 +90,9 @@ def wino_wanted(w, mode):
     if mode not in (0, 1) or w.dim() != 4 or w.shape[2:] != (3, 3) or _FP32_MATH != "split6":
         return False
     n, c = (w.shape[0], w.shape[1]) if mode == 0 else (w.shape[1], w.shape[0])
-    # csrc wino_ok: a 64-channel reduction into more than 64 outputs only on 128-channel items
-    return c % 32 == 0 and n % 64 == 0 and (c >= 128 or n <= 64 or (_WINO128 and n % 128 == 0))
+    # mirrors csrc/winograd.hip wino_ok / wino_wide_items: a short reduction (c < 128) into more
+    # than 64 outputs runs only as wide 128-channel items
+    return c % 32 == 0 and n % 64 == 0 and (c >= 128 or n <= 64 or n % 128 == 0)
 
 
 def pack_wino(jobs):

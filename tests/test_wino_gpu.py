@@ -43,21 +43,24 @@ def check(name, got, cpu32, ref64):
 CASES = [
     # B, H, W, c0, c1, cout
     (2, 16, 16, 64, 0, 64),       # one block of 64 tiles x 2 images
-    (3, 10, 14, 128, 0, 128),     # 105 tiles: a partial second tile block, 2 channel blocks, non-square
-    (2, 8, 8, 64, 64, 64),        # concat (two sources), every tile on an image edge
+    (3, 10, 14, 128, 0, 128),     # 105 tiles: a ragged second tile block, 2 channel blocks, non-square
+    (2, 8, 8, 64, 64, 64),        # concat (two sources), every tile on an image edge; wide-item dgrad
     (1, 32, 16, 128, 0, 192),     # 3 channel blocks, 8 chunks
     (4, 8, 8, 512, 0, 512),       # split-K (bottom level shape): 64 tiles, 8 channel blocks
     (2, 16, 16, 256, 256, 256),   # split-K with two sources (the 16x16 up level)
     (1, 2, 2, 32, 0, 64),         # a single 2x2 tile
-    # > 256 items: the persistent kernel (items streamed per block, next-item prefetch during the
-    # epilogue, per-XCD item ranges)
-    (5, 128, 128, 64, 0, 64),     # 320 items, 40 per XCD
-    (3, 96, 80, 128, 0, 192),     # 270 items: ragged per-XCD ranges (270 % 8 = 6), 3 channel blocks
-    # n % 128 == 0 shapes (the 128-channel items under PU_WINO128=1 - test_wino128_bit_identical_..)
-    (2, 16, 16, 128, 0, 256),     # 2 channel blocks of 128
-    (5, 128, 128, 64, 0, 128),    # 64 -> 128 (direct before 128-channel items), 640 items, persistent
-    (7, 96, 80, 128, 0, 128),     # 420 items: ragged per-XCD ranges (420 % 8 = 4)
-    (2, 24, 24, 64, 64, 64),      # its data gradient: 64 -> 128 split at 64 (the top concat layer)
+    # many items of wino4_x6_kernel (one per block): more blocks than CUs, so the XCD-aware item
+    # order wraps
+    (5, 128, 128, 64, 0, 64),     # 320 items of 64 x 64
+    (3, 96, 80, 128, 0, 192),     # 270 items (not a multiple of the 8 XCDs), 3 channel blocks
+    # n % 128 == 0 shapes: 64 x 64 items when C >= 128, wide (32-tile x 128-channel) items when C < 128
+    (2, 16, 16, 128, 0, 256),     # 4 channel blocks of 64
+    (5, 128, 128, 64, 0, 128),    # 64 -> 128 forward on wide items: 640 items
+    (7, 96, 80, 128, 0, 128),     # 420 items (420 % 8 = 4), 2 channel blocks
+    (2, 24, 24, 64, 64, 64),      # its data gradient 64 -> 128 split at 64 (the top concat layer): wide
+                                  # items whose two 32-channel block pairs go to different destinations
+    (2, 24, 24, 128, 128, 128),   # concat forward on 64 x 64 items; data gradient 128 -> 256 split at 128
+    (3, 16, 16, 64, 0, 128),      # wide items forward (6 items of 32 tiles); data gradient 128 -> 64
 ]
 
 
@@ -98,16 +101,44 @@ def test_wino_fwd_dgrad_vs_fp64(B, H, W, c0, c1, cout):
         K.set_wino(prev)
 
 
-def test_wino_resid_and_accumulate_epilogues():
-    """RESID (the residual add before the ReLU) and ACCUM through the Winograd epilogue, against
-    the direct kernel on the same layer (both within fp32 rounding of each other)."""
+def _wino_plan(B, H, W, C, N, x, packed, k_pad, dst, bias=None, resid=None, relu=False, accum=False):
+    """(mode, item channels, ksplit) pu_conv_igemm_tile reports for the call K.igemm makes with
+    these operands (mode 6 = the Winograd kernel), with the split-K workspace K.igemm would pass."""
+    import ctypes
+    from punet import _lib
+    flags = (_lib.PU_EPI_RELU if relu else 0) | (_lib.PU_EPI_ACCUM if accum else 0) | \
+        (_lib.PU_EPI_RESID if resid is not None else 0)
+    a = _lib.ConvArgs(B, H, W, H, W, 3, 3, 1, 1, x.data_ptr(), C, None, 0, packed.data_ptr(), k_pad,
+                      K.cgroup_for(C), N, None if bias is None else bias.data_ptr(), dst.data_ptr(), N, None,
+                      None, None, flags, None, 0, None if resid is None else resid.data_ptr())
+    a.weight6 = packed._split6.data_ptr()
+    a.wino = packed._wino.data_ptr()
+    L = K.lib()
+    nbytes = L.pu_conv_igemm_workspace_bytes(ctypes.byref(a))
+    if nbytes:      # planning only reads the pointer's presence and the size
+        a.workspace, a.ws_bytes = dst.data_ptr(), nbytes
+    bm, bn, mode, ks = (ctypes.c_int() for _ in range(4))
+    assert L.pu_conv_igemm_tile(ctypes.byref(a), *(ctypes.byref(v) for v in (bm, bn, mode, ks))) == 0
+    return mode.value, bn.value, ks.value
+
+
+def _resid_and_accumulate(B, H, W, C, N, item_n, split):
+    """RESID (the residual add before the ReLU) and ACCUM through the Winograd kernel's general
+    epilogue (the FULL instantiations) or, with split, through the split-K finish: against fp64
+    next to ATen's CPU fp32 error, and against the direct kernel on the same layer (both within
+    fp32 rounding of each other).  Each call really takes the Winograd kernel with item_n-channel
+    items."""
     g = torch.Generator().manual_seed(11)
-    B, H, W, C, N = 2, 12, 8, 64, 64
-    x = torch.randn(B, H, W, C, generator=g).to(DEV)
-    w = (torch.randn(N, C, 3, 3, generator=g) * 0.05).to(DEV)
-    b = torch.randn(N, generator=g).to(DEV)
-    r = torch.randn(B, H, W, N, generator=g).to(DEV)
-    acc0 = torch.randn(B, H, W, N, generator=g).to(DEV)
+    x = torch.randn(B, H, W, C, generator=g)
+    w = torch.randn(N, C, 3, 3, generator=g) * 0.05
+    b = torch.randn(N, generator=g)
+    r = torch.randn(B, H, W, N, generator=g)
+    acc0 = torch.randn(B, H, W, N, generator=g)
+    ref = {}
+    for dt in (torch.float32, torch.float64):
+        z = F.conv2d(nchw(x).to(dt), w.to(dt), None, padding=1)
+        ref[dt] = (torch.relu(z + b.to(dt).view(1, N, 1, 1) + nchw(r).to(dt)), nchw(acc0).to(dt) + z)
+    x, w, b, r, acc0 = (t.to(DEV) for t in (x, w, b, r, acc0))
     outs = {}
     for on in (True, False):
         prev = K.set_wino(on)
@@ -115,18 +146,41 @@ def test_wino_resid_and_accumulate_epilogues():
             pk = T._Packs()
             k_pad = K.round16(9 * C)
             packed = pk.get(w, 0, k_pad, K.cgroup_for(C))
-            assert (getattr(packed, "_wino", None) is not None) == on or not on
+            assert (getattr(packed, "_wino", None) is not None) == on
             o1 = torch.empty(B, H, W, N, device=DEV)
+            o2 = acc0.clone()
+            if on:
+                for plan in (_wino_plan(B, H, W, C, N, x, packed, k_pad, o1, bias=b, resid=r, relu=True),
+                             _wino_plan(B, H, W, C, N, x, packed, k_pad, o2, accum=True)):
+                    assert plan[:2] == (6, item_n), plan
+                    assert (plan[2] >= 2) == split, plan
             K.igemm(batch=B, in_hw=(H, W), out_hw=(H, W), k=3, stride=1, pad=1, src0=x, c0=C, weight=packed,
                     k_pad=k_pad, n=N, bias=b, dst0=o1, relu=True, resid=r, cgroup=K.cgroup_for(C))
-            o2 = acc0.clone()
             K.igemm(batch=B, in_hw=(H, W), out_hw=(H, W), k=3, stride=1, pad=1, src0=x, c0=C, weight=packed,
                     k_pad=k_pad, n=N, dst0=o2, accum=True, cgroup=K.cgroup_for(C))
             outs[on] = (o1.cpu(), o2.cpu())
         finally:
             K.set_wino(prev)
+    shape = "%dx%dx%d %d->%d" % (B, H, W, C, N)
+    for i, name in enumerate(("wino resid+relu " + shape, "wino accumulate " + shape)):
+        check(name, nchw(outs[True][i]), ref[torch.float32][i], ref[torch.float64][i])
     for a, bb in zip(outs[True], outs[False]):
         torch.testing.assert_close(a, bb, rtol=1e-5, atol=2e-5 * bb.abs().max().item())
+
+
+def test_wino_resid_and_accumulate_epilogues():
+    """wino4_x6_kernel<true, 2>: one 64 x 64 item, 48 of its 64 tiles."""
+    _resid_and_accumulate(2, 12, 8, 64, 64, 64, False)
+
+
+@pytest.mark.parametrize("B,H,W,C,N,item_n,split", [
+    (1, 4, 4, 64, 128, 128, False),    # <true, 4>: one ragged wide item of 4 tiles
+    (2, 16, 8, 64, 128, 128, False),   # <true, 4>: two full wide items
+    (1, 8, 8, 256, 64, 64, True),      # 16 tiles, 16 chunks: a 2-way K split, so the residual and the
+                                       # ReLU run in igemm_splitk_epilogue_kernel
+])
+def test_wino_resid_and_accumulate_epilogues_wide_and_split_k(B, H, W, C, N, item_n, split):
+    _resid_and_accumulate(B, H, W, C, N, item_n, split)
 
 
 def test_pack_wino_is_G_g_Gt_split_exactly():
@@ -146,43 +200,6 @@ def test_pack_wino_is_G_g_Gt_split_exactly():
         got = planes.permute(1, 2, 3, 0, 4).reshape(16, 3, n, c)
         assert torch.equal(got[:, 0] + got[:, 1] + got[:, 2], U), dgrad
         assert torch.equal(got[:, 0], U.bfloat16().float())
-
-
-_PERSIST_SCRIPT = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[2])
-from punet import kernels as K, trunk as T
-B, H, W, C, N = 5, 128, 128, 64, 64
-g = torch.Generator().manual_seed(77)
-x = torch.randn(B, H, W, C, generator=g).relu().cuda()
-w = (torch.randn(N, C, 3, 3, generator=g) * 0.06).cuda()
-b = torch.randn(N, generator=g).cuda()
-dz = torch.randn(B, H, W, N, generator=g).cuda()
-pk = T._Packs()
-y = T.conv3x3(x, w, b, pk, relu=True)
-d0, _ = T.conv3x3_dgrad(dz, w, pk, mask0=x)
-torch.save({"y": y.cpu(), "d": d0.cpu()}, sys.argv[1])
-"""
-
-
-def test_wino_persistent_equals_one_item_per_block(tmp_path):
-    """The persistent kernel (320 items on 256 blocks) and the one-item-per-block launch
-    (PU_WINO_PERSIST=0, read once per process - hence two child processes) form the same per-item
-    sums in the same order: forward and data gradient bit-identical."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "plastic-unet_amd")
-    out = {}
-    for persist in ("1", "0"):
-        f = str(tmp_path / ("p%s.pt" % persist))
-        env = dict(os.environ, PU_WINO_PERSIST=persist, PU_WINO="1", PU_WINO4="0")   # the 8-wave kernel's modes
-        r = subprocess.run([sys.executable, "-c", _PERSIST_SCRIPT, f, root], env=env, capture_output=True,
-                           text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        out[persist] = torch.load(f, weights_only=True)
-    assert torch.equal(out["1"]["y"], out["0"]["y"])
-    assert torch.equal(out["1"]["d"], out["0"]["d"])
 
 
 WGRAD_CASES = [
@@ -220,159 +237,3 @@ def test_wino_wgrad_vs_fp64(B, H, W, c0, c1, cout):
     check("wino bias grad", db, ref[torch.float32][1], ref[torch.float64][1])
     dw2, db2 = T.conv3x3_wgrad(dzk, x0, x1)
     assert torch.equal(dw, dw2) and torch.equal(db, db2), "Winograd weight gradient is not deterministic"
-
-
-_W128_SCRIPT = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[2])
-from punet import kernels as K, trunk as T
-out = {}
-for (B, H, W, c0, c1, N) in [(3, 32, 24, 128, 0, 128), (2, 16, 16, 256, 0, 256), (2, 32, 32, 128, 128, 128),
-                             (4, 8, 8, 512, 0, 512), (9, 64, 64, 128, 0, 128)]:
-    g = torch.Generator().manual_seed(B + H + c0 + c1 + N)
-    C = c0 + c1
-    x = torch.randn(B, H, W, C, generator=g).relu().cuda()
-    w = (torch.randn(N, C, 3, 3, generator=g) * 0.05).cuda()
-    b = torch.randn(N, generator=g).cuda()
-    dz = torch.randn(B, H, W, N, generator=g).cuda()
-    pk = T._Packs()
-    x0, x1 = (x[..., :c0].contiguous(), x[..., c0:].contiguous()) if c1 else (x, None)
-    y = T.conv3x3(x0, w, b, pk, x1=x1, relu=True)
-    d0, d1 = T.conv3x3_dgrad(dz, w, pk, split=c0 if c1 else None, mask0=x0, mask1=x1)
-    out[(B, H, W, c0, c1, N)] = (y.cpu(), d0.cpu(), None if d1 is None else d1.cpu())
-torch.save(out, sys.argv[1])
-"""
-
-
-def test_wino128_bit_identical_to_64_channel_items(tmp_path):
-    """32-tile x 128-channel Winograd items (wino128_x6_kernel) and 64 x 64 items (PU_WINO128=0,
-    read once per process - two child processes) feed every accumulator the same U / V fragments
-    in the same MFMA order, then the same output transform: forward and data gradient bitwise equal
-    on the layers both take (n % 128 == 0, C >= 128; split-K, concat sources, split outputs,
-    persistent item streams)."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "plastic-unet_amd")
-    res = {}
-    for on in ("1", "0"):
-        f = str(tmp_path / ("w%s.pt" % on))
-        env = dict(os.environ, PU_WINO4="0", PU_WINO128=on, PU_WINO="1")
-        r = subprocess.run([sys.executable, "-c", _W128_SCRIPT, f, root], env=env, capture_output=True, text=True,
-                           timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res[on] = torch.load(f, weights_only=True)
-    for k in res["1"]:
-        for a, b in zip(res["1"][k], res["0"][k]):
-            assert (a is None) == (b is None), k
-            if a is not None:
-                assert torch.equal(a, b), k
-
-
-_W4_SCRIPT = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[2])
-from punet import kernels as K, trunk as T
-out = {}
-for (B, H, W, c0, c1, N) in [(2, 16, 16, 64, 0, 64), (3, 10, 14, 128, 0, 128), (2, 8, 8, 64, 64, 64),
-                             (1, 32, 16, 128, 0, 192), (4, 8, 8, 512, 0, 512), (2, 16, 16, 256, 256, 256),
-                             (1, 2, 2, 32, 0, 64), (5, 128, 128, 64, 0, 64), (3, 96, 80, 128, 0, 192),
-                             (2, 24, 24, 128, 128, 128), (2, 24, 24, 64, 64, 64), (3, 16, 16, 64, 0, 128)]:
-    g = torch.Generator().manual_seed(B + H + W + c0 + c1 + N)
-    C = c0 + c1
-    x = torch.randn(B, H, W, C, generator=g).relu().cuda()
-    w = (torch.randn(N, C, 3, 3, generator=g) * 0.05).cuda()
-    b = torch.randn(N, generator=g).cuda()
-    dz = torch.randn(B, H, W, N, generator=g).cuda()
-    r = torch.randn(B, H, W, N, generator=g).cuda()
-    a0 = torch.randn(B, H, W, N, generator=g).cuda()
-    pk = T._Packs()
-    x0, x1 = (x[..., :c0].contiguous(), x[..., c0:].contiguous()) if c1 else (x, None)
-    y = T.conv3x3(x0, w, b, pk, x1=x1, relu=True)
-    d0, d1 = T.conv3x3_dgrad(dz, w, pk, split=c0 if c1 else None, mask0=x0, mask1=x1)
-    res = [y.cpu(), d0.cpu(), None if d1 is None else d1.cpu()]
-    if not c1:     # the general epilogue: residual + ReLU, accumulate
-        k_pad = K.round16(9 * C)
-        packed = pk.get(w, 0, k_pad, K.cgroup_for(C))
-        o1 = torch.empty(B, H, W, N, device="cuda")
-        K.igemm(batch=B, in_hw=(H, W), out_hw=(H, W), k=3, stride=1, pad=1, src0=x, c0=C, weight=packed,
-                k_pad=k_pad, n=N, bias=b, dst0=o1, relu=True, resid=r, cgroup=K.cgroup_for(C))
-        o2 = a0.clone()
-        K.igemm(batch=B, in_hw=(H, W), out_hw=(H, W), k=3, stride=1, pad=1, src0=x, c0=C, weight=packed,
-                k_pad=k_pad, n=N, dst0=o2, accum=True, cgroup=K.cgroup_for(C))
-        res += [o1.cpu(), o2.cpu()]
-    out[(B, H, W, c0, c1, N)] = res
-torch.save(out, sys.argv[1])
-"""
-
-
-def test_wino4_bit_identical_to_8_wave_kernel(tmp_path):
-    """wino4_x6_kernel (one wave per SIMD, 2 x 2 or 4 x 1 MFMA blocks per position - 64 x 64 or, for
-    n % 128 == 0, 32-tile x 128-channel items -, U from L2 into registers) and wino_x6_kernel
-    (PU_WINO4=0; read once per process - two child processes) form
-    every accumulator from the same U / V planes in the same product order and run the same
-    output-transform expression tree: forward, data gradient (masks, concat split), residual and
-    accumulate epilogues bitwise equal - one and many items per block, split-K, concat sources,
-    ragged tile blocks."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "plastic-unet_amd")
-    res = {}
-    # (PU_WINO4, PU_WINO4_WIDE, PU_WINO128): the short-reduction concat data gradients take the
-    # direct kernel in "100" / "000" and 128-channel Winograd items in the others
-    for on in ("100", "000", "110", "120", "001"):
-        f = str(tmp_path / ("w%s.pt" % on))
-        env = dict(os.environ, PU_WINO4=on[0], PU_WINO4_WIDE=on[1], PU_WINO128=on[2], PU_WINO="1")
-        r = subprocess.run([sys.executable, "-c", _W4_SCRIPT, f, root], env=env, capture_output=True, text=True,
-                           timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res[on] = torch.load(f, weights_only=True)
-    for v, ref in (("100", "000"), ("110", "001"), ("120", "001")):
-        for k in res[v]:
-            for i, (a, b) in enumerate(zip(res[v][k], res[ref][k])):
-                assert (a is None) == (b is None), k
-                if a is not None:
-                    assert torch.equal(a, b), (v, k, i, (a - b).abs().max().item())
-
-
-_WW4_SCRIPT = r"""
-import sys, torch
-sys.path.insert(0, sys.argv[2])
-from punet import kernels as K, trunk as T
-out = {}
-for (B, H, W, c0, c1, N) in [(2, 16, 16, 64, 0, 64), (3, 10, 14, 128, 0, 128), (2, 8, 8, 64, 64, 64),
-                             (1, 32, 16, 128, 0, 192), (4, 8, 8, 512, 0, 512), (2, 16, 16, 256, 256, 256),
-                             (8, 64, 64, 64, 0, 64), (1, 2, 2, 64, 0, 64)]:
-    g = torch.Generator().manual_seed(B + H + W + c0 + c1 + N)
-    C = c0 + c1
-    x = torch.randn(B, H, W, C, generator=g).relu().cuda()
-    dz = (torch.randn(B, H, W, N, generator=g) * (torch.rand(B, H, W, N, generator=g) > 0.3).float()).cuda()
-    x0, x1 = (x[..., :c0].contiguous(), x[..., c0:].contiguous()) if c1 else (x, None)
-    dw, db = T.conv3x3_wgrad(dz, x0, x1)
-    out[(B, H, W, c0, c1, N)] = (dw.cpu(), db.cpu())
-torch.save(out, sys.argv[1])
-"""
-
-
-def test_wgrad_wino4_bit_identical_to_8_wave_kernel(tmp_path):
-    """wgrad_wino4_x6_kernel (one wave per SIMD, 2 x 2 channel blocks per position, 4-channel
-    producer threads, a 4-wave R exchange in the output transform; PU_WW4=1) and
-    wgrad_wino_x6_kernel form the same planes, run the same 6 products per accumulator in the same
-    order and the same G^T M G expression tree: weight and bias gradients bitwise equal - ragged
-    stages, concat sources, several channel blocks, split slabs, a single tile."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "plastic-unet_amd")
-    res = {}
-    for on in ("1", "0"):
-        f = str(tmp_path / ("ww%s.pt" % on))
-        env = dict(os.environ, PU_WW4=on)
-        r = subprocess.run([sys.executable, "-c", _WW4_SCRIPT, f, root], env=env, capture_output=True, text=True,
-                           timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res[on] = torch.load(f, weights_only=True)
-    for k in res["1"]:
-        for i, (a, b) in enumerate(zip(res["1"][k], res["0"][k])):
-            assert torch.equal(a, b), (k, i, (a - b).abs().max().item())

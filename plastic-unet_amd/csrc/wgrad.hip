@@ -1540,116 +1540,83 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const WgradParams p) {
     }
 }
 
-// Split-K reduction, pass 1: part[g][idx] = sum over splits z = g, g+G, ... of slab[z][idx]
-// (fp64, 4 independent accumulators so each thread keeps several loads in flight).
-__global__ void wgrad_sum_splits_kernel(const float* __restrict__ slab, int splits, long long total, int G,
-                                        double* __restrict__ part) {
-    const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int g = blockIdx.y;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int z = g;
-    for (; z + 3 * G < splits; z += 4 * G) {
-        s0 += slab[(long long)z * total + idx];
-        s1 += slab[(long long)(z + G) * total + idx];
-        s2 += slab[(long long)(z + 2 * G) * total + idx];
-        s3 += slab[(long long)(z + 3 * G) * total + idx];
-    }
-    for (; z < splits; z += G) s0 += slab[(long long)z * total + idx];
-    part[(long long)g * total + idx] = (s0 + s1) + (s2 + s3);
+// ------------------------------------------------------------------ phase 2: the split reduction
+// Every slab row is Kcp = ceil4(Kc) floats (plan_dims), so the reduction works on quads of 4
+// consecutive entries of one row.
+//
+// The one summation order of phase 2.  `count` partials, `stride` elements of V apart, go into 4
+// fp64 chains: partial i to chain i & 3 while i < 4 * (count / 4), the remainder to chain 0; the
+// result is (s0 + s1) + (s2 + s3).  V is float, double or a quad of either (summed per
+// component).  DEPTH (4 or 8) is only how many loads are issued before their adds: 8 takes two
+// chain rounds at once, then one round of 4 if it is left - the same order, so every kernel below
+// gives the same bits for the same sequence of partials.
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ double widen(float v) { return (double)v; }
+__device__ __forceinline__ double widen(double v) { return v; }
+__device__ __forceinline__ f64x4 widen(f32x4 v) { return __builtin_convertvector(v, f64x4); }
+__device__ __forceinline__ f64x4 widen(f64x4 v) { return v; }
+
+template <int R, typename V, typename A>
+__device__ __forceinline__ void chain_round(A (&s)[4], const V* p, long long stride) {
+    V v[R];
+#pragma unroll
+    for (int c = 0; c < R; ++c) v[c] = p[c * stride];
+#pragma unroll
+    for (int c = 0; c < R; ++c) s[c & 3] += widen(v[c]);
 }
 
-// pass 1 on float4 quads (total % 4 == 0): the same 4 chains per entry in the same order (so
-// bit-identical to wgrad_sum_splits_kernel), with two chain rounds' 8 x 16-B loads issued before
-// their adds - the scalar form kept 4 x 4 B per thread in flight and ran at ~1.3 TB/s.
+template <int DEPTH, typename V>
+__device__ __forceinline__ auto sum_chains(const V* p, int count, long long stride) -> decltype(widen(*p)) {
+    static_assert(DEPTH == 4 || DEPTH == 8, "sum_chains: 4 or 8 loads in flight");
+    decltype(widen(*p)) s[4] = {};
+    int i = 0;
+    for (; i + DEPTH <= count; i += DEPTH, p += DEPTH * stride) chain_round<DEPTH>(s, p, stride);
+    if (DEPTH == 8 && i + 4 <= count) {
+        chain_round<4>(s, p, stride);
+        i += 4;
+        p += 4 * stride;
+    }
+    for (; i < count; ++i, p += stride) s[0] += widen(*p);
+    return (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// entry (n, k) of the reduced slab -> dweight[n][c][r][ss] (k = tap * C + c, tap = r * kw + ss), or
+// dbias[n] for the bias column k == K of bias_mode 1; the pad columns above it are dropped
+__device__ __forceinline__ void store_oihw(int n, int k, float v, int K, int C, int kh, int kw, int bias_mode,
+                                           float* __restrict__ dw, float* __restrict__ db, int accumulate) {
+    if (k < K) {
+        const int tap = k / C, c = k - tap * C;
+        const int r = tap / kw, ss = tap - r * kw;
+        float* o = dw + (((long long)n * C + c) * kh + r) * kw + ss;
+        *o = accumulate ? *o + v : v;
+    } else if (bias_mode == 1 && k == K) {
+        db[n] = accumulate ? db[n] + v : v;
+    }
+}
+
+// pass 1 of the grouped form: part[g][idx] = sum over splits z = g, g + G, ... of slab[z][idx], a
+// quad per thread with 8 x 16-B loads in flight (4 x 4 B per thread ran at ~1.3 TB/s)
 __global__ __launch_bounds__(256) void wgrad_sum_splits4_kernel(const float* __restrict__ slab, int splits,
                                                                 long long total, int G, double* __restrict__ part) {
     const long long idx = 4 * (blockIdx.x * (long long)blockDim.x + threadIdx.x);
     if (idx >= total) return;
     const int g = blockIdx.y;
-    double s[4][4] = {};
-    const float* sp = slab + idx;
-    int z = g;
-    for (; z + 7 * G < splits; z += 8 * G) {
-        f32x4 v[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) v[c] = *reinterpret_cast<const f32x4*>(sp + (long long)(z + c * G) * total);
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s[c & 3][e] += (double)v[c][e];
-    }
-    if (z + 3 * G < splits) {
-        f32x4 v[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = *reinterpret_cast<const f32x4*>(sp + (long long)(z + c * G) * total);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s[c][e] += (double)v[c][e];
-        z += 4 * G;
-    }
-    for (; z < splits; z += G) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(sp + (long long)z * total);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[0][e] += (double)v[e];
-    }
+    const f64x4 s = sum_chains<8>(reinterpret_cast<const f32x4*>(slab + (long long)g * total + idx),
+                                  (splits - g + G - 1) / G, G * (total >> 2));
     double* o = part + (long long)g * total + idx;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (s[0][e] + s[1][e]) + (s[2][e] + s[3][e]);
+    for (int e = 0; e < 4; ++e) o[e] = s[e];
 }
 
-// pass 2: sum the G groups (fixed order, fp64) and scatter to PyTorch's [n][c][kh][kw] + bias.
-// Threads [0, total) handle slab entries; threads [total, total + C) the ConvT bias (mode 2).
+// pass 2, quad finisher: sum the G partials of 4 consecutive entries of one slab row (8 quads in
+// flight) and scatter them to PyTorch's [n][c][kh][kw] + bias.  Threads [0, total / 4) take the
+// quads, threads [total / 4, total / 4 + C) the ConvT bias (mode 2).
 // T = double: the G pass-1 partials;  T = float: the slab itself (G = splits, single pass).
-template <typename T>
-__global__ void wgrad_finish_kernel(const T* __restrict__ part, int G, int Nr, int Kc, int N, int K, int C,  // Kc = slab row stride
-                                    int kh, int kw, int bias_mode, float* __restrict__ dw, float* __restrict__ db,
-                                    int accumulate) {
-    const long long total = (long long)Nr * Kc;
-    const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (idx < total) {
-        const int n = int(idx / Kc);
-        const int k = int(idx - (long long)n * Kc);
-        if (n >= N) return;
-        // 4 independent fp64 chains (fixed interleave, deterministic): keeps 4 loads in flight
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        int g = 0;
-        for (; g + 3 < G; g += 4) {
-            s0 += (double)part[(long long)g * total + idx];
-            s1 += (double)part[(long long)(g + 1) * total + idx];
-            s2 += (double)part[(long long)(g + 2) * total + idx];
-            s3 += (double)part[(long long)(g + 3) * total + idx];
-        }
-        for (; g < G; ++g) s0 += (double)part[(long long)g * total + idx];
-        const float v = (float)((s0 + s1) + (s2 + s3));
-        if (k < K) {
-            const int tap = k / C, c = k - tap * C;
-            const int r = tap / kw, ss = tap - r * kw;
-            float* o = dw + (((long long)n * C + c) * kh + r) * kw + ss;
-            *o = accumulate ? *o + v : v;
-        } else if (bias_mode == 1 && k == K) {
-            db[n] = accumulate ? db[n] + v : v;
-        }
-    } else if (bias_mode == 2 && idx < total + C) {
-        const int c = int(idx - total);
-        double s = 0.0;
-        for (int t = 0; t < kh * kw; ++t)
-            for (int g = 0; g < G; ++g) s += (double)part[(long long)g * total + (long long)N * Kc + t * C + c];
-        const float v = (float)s;
-        db[c] = accumulate ? db[c] + v : v;
-    }
-}
-
-// wgrad_finish_kernel on quads of 4 consecutive entries of one slab row (Kc % 4 == 0): the same
-// 4 fp64 chains per entry in the same order - bit-identical to wgrad_finish_kernel for the WEIGHT
-// entries (and the bias of modes 0/1), 8 partial quads in flight per thread instead of 4 scalars.
-// The ConvT bias (mode 2: entries t*C + c of row N over every tap t and partial g) is NOT summed in
-// the scalar kernel's order: it runs as 4 interleaved fp64 chains over the flattened (t, g)
-// sequence with 8 loads in flight (the scalar form's one dependent chain of taps x G loads was a
-// latency tail, 17.7 us for a 64-channel ConvT in C2), so it can differ from the scalar kernel's
-// result in the last fp32 ulp.  It is deterministic run to run (fixed order; pinned by
-// tests/test_kernels_gpu.py::test_convT_bias_grad_run_to_run_bitwise).
+// The ConvT bias (mode 2: entries t*C + c of row N over every tap t and partial g) has an order
+// of its own: 4 interleaved fp64 chains over the flattened (t, g) sequence with 8 loads in flight,
+// everything after the last whole 8-round on chain 0 (one dependent chain of taps x G loads was a
+// latency tail, 17.7 us for a 64-channel ConvT in C2).  It is deterministic run to run (fixed
+// order; pinned by tests/test_kernels_gpu.py::test_convT_bias_grad_run_to_run_bitwise).
 template <typename T>
 __global__ __launch_bounds__(256) void wgrad_finish4_kernel(const T* __restrict__ part, int G, int Nr, int Kc, int N,
                                                             int K, int C, int kh, int kw, int bias_mode,
@@ -1664,46 +1631,9 @@ __global__ __launch_bounds__(256) void wgrad_finish4_kernel(const T* __restrict_
         const int n = int(idx / Kc);
         const int k0 = int(idx - (long long)n * Kc);
         if (n >= N) return;
-        const T* sp = part + idx;
-        double s[4][4] = {};
-        int g = 0;
-        for (; g + 7 < G; g += 8) {
-            t4 v[8];
+        const f64x4 s = sum_chains<8>(reinterpret_cast<const t4*>(part + idx), G, nq);
 #pragma unroll
-            for (int c = 0; c < 8; ++c) v[c] = *reinterpret_cast<const t4*>(sp + (long long)(g + c) * total);
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) s[c & 3][e] += (double)v[c][e];
-        }
-        if (g + 3 < G) {
-            t4 v[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) v[c] = *reinterpret_cast<const t4*>(sp + (long long)(g + c) * total);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) s[c][e] += (double)v[c][e];
-            g += 4;
-        }
-        for (; g < G; ++g) {
-            const t4 v = *reinterpret_cast<const t4*>(sp + (long long)g * total);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s[0][e] += (double)v[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int k = k0 + e;
-            const float v = (float)((s[0][e] + s[1][e]) + (s[2][e] + s[3][e]));
-            if (k < K) {
-                const int tap = k / C, c = k - tap * C;
-                const int r = tap / kw, ss = tap - r * kw;
-                float* o = dw + (((long long)n * C + c) * kh + r) * kw + ss;
-                *o = accumulate ? *o + v : v;
-            } else if (bias_mode == 1 && k == K) {
-                db[n] = accumulate ? db[n] + v : v;
-            }
-        }
+        for (int e = 0; e < 4; ++e) store_oihw(n, k0 + e, (float)s[e], K, C, kh, kw, bias_mode, dw, db, accumulate);
     } else if (bias_mode == 2 && q < nq + C) {
         const int c = int(q - nq);
         const int J = kh * kw * G;                       // j = t * G + g
@@ -1730,9 +1660,9 @@ __global__ __launch_bounds__(256) void wgrad_finish4_kernel(const T* __restrict_
 // pass 2 with coalesced stores: block (chunk of 256 channels, row n) sums slab[.][n][tap*C + c]
 // for its channels x taps (thread = (tap, 4 channels): 1-KB float4 reads per wave and split),
 // transposes through LDS and stores the contiguous [c][kh][kw] run of dweight[n] as float4 (the
-// scatter above writes 4 B at a 4*taps-byte stride).  Same fixed-order fp64 chains as
-// wgrad_finish_kernel, so bit-identical.  C % 4 == 0, 16-B aligned rows; bias_mode 0/1 (the ConvT
-// bias, mode 2, stays on wgrad_finish_kernel).
+// scatter above writes 4 B at a 4*taps-byte stride).  The same sum_chains per entry as the quad
+// finisher (4 loads in flight), so bit-identical to it.  C % 4 == 0, 16-B aligned rows;
+// bias_mode 0/1 (the ConvT bias, mode 2, stays on wgrad_finish4_kernel).
 template <typename T>
 __global__ __launch_bounds__(576) void wgrad_finish_t_kernel(const T* __restrict__ part, int G, int Nr, int Kc, int K,
                                                               int C, int taps, int bias_mode, float* __restrict__ dw,
@@ -1746,42 +1676,12 @@ __global__ __launch_bounds__(576) void wgrad_finish_t_kernel(const T* __restrict
     const int cn = min(256, C - c0);
     if (cq < cn) {
         const long long idx = (long long)n * Kc + tap * C + c0 + cq;
-        double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
-        double s2[4] = {0.0, 0.0, 0.0, 0.0}, s3[4] = {0.0, 0.0, 0.0, 0.0};
-        int g = 0;
-        for (; g + 3 < G; g += 4) {
-            const t4 a = *reinterpret_cast<const t4*>(part + (long long)g * total + idx);
-            const t4 b = *reinterpret_cast<const t4*>(part + (long long)(g + 1) * total + idx);
-            const t4 c = *reinterpret_cast<const t4*>(part + (long long)(g + 2) * total + idx);
-            const t4 d = *reinterpret_cast<const t4*>(part + (long long)(g + 3) * total + idx);
+        const f64x4 s = sum_chains<4>(reinterpret_cast<const t4*>(part) + (idx >> 2), G, total >> 2);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                s0[e] += (double)a[e];
-                s1[e] += (double)b[e];
-                s2[e] += (double)c[e];
-                s3[e] += (double)d[e];
-            }
-        }
-        for (; g < G; ++g) {
-            const t4 a = *reinterpret_cast<const t4*>(part + (long long)g * total + idx);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s0[e] += (double)a[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) tr[(cq + e) * taps + tap] = (float)((s0[e] + s1[e]) + (s2[e] + s3[e]));
+        for (int e = 0; e < 4; ++e) tr[(cq + e) * taps + tap] = (float)s[e];
     }
     if (bias_mode == 1 && blockIdx.x == 0 && threadIdx.x == 0) {
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        const long long idx = (long long)n * Kc + K;
-        int g = 0;
-        for (; g + 3 < G; g += 4) {
-            s0 += (double)part[(long long)g * total + idx];
-            s1 += (double)part[(long long)(g + 1) * total + idx];
-            s2 += (double)part[(long long)(g + 2) * total + idx];
-            s3 += (double)part[(long long)(g + 3) * total + idx];
-        }
-        for (; g < G; ++g) s0 += (double)part[(long long)g * total + idx];
-        const float v = (float)((s0 + s1) + (s2 + s3));
+        const float v = (float)sum_chains<4>(part + (long long)n * Kc + K, G, total);
         db[n] = accumulate ? db[n] + v : v;
     }
     __syncthreads();
@@ -1842,6 +1742,39 @@ static void plan_groups(WgradPlan* pl) {
     pl->G = G < 1 ? 1 : G;
 }
 
+// the GEMM's dimensions and the slab's shape, fp32 and bf16 alike: M pixel rows, K = taps x C,
+// Nr x Kc slab entries with the bias as row N (mode 2) or column K (mode 1).  Kcp, the slab's row
+// stride, is Kc rounded up to 4 floats: phase 2 reads and sums every slab as 16-byte quads.
+static int plan_dims(const pu_wgrad_args* a, WgradPlan* pl, const char* who) {
+    const long long M = (long long)a->batch * a->out_h * a->out_w;
+    PU_REQUIRE(M < (1LL << 31), "%s: too many pixels", who);
+    pl->M = (int)M;
+    pl->C = a->c0 + a->c1;
+    pl->K = a->kh * a->kw * pl->C;
+    pl->Nr = a->n + (a->bias_mode == 2 ? 1 : 0);
+    pl->Kc = pl->K + (a->bias_mode == 1 ? 1 : 0);
+    pl->Kcp = (pl->Kc + 3) / 4 * 4;
+    return PU_OK;
+}
+
+// the halo kernels (wgrad_halo_x6_kernel, wgrad_halo_bf16_kernel): 64 NT x 64 x 9-tap tiles,
+// 16-pixel stages split so that one round of blocks fills the chip
+static void plan_halo(const pu_wgrad_args* a, WgradPlan* pl) {
+    pl->halo = true;
+    pl->nt = a->n % 128 == 0 ? 2 : 1;    // 128 output channels per block when they divide
+    pl->BN = 64 * pl->nt;
+    pl->BK = 9 * 64;
+    pl->gx = pl->C / 64;
+    pl->gy = a->n / pl->BN;
+    int splits = (pl->nt == 2 ? 256 : 512) / (pl->gx * pl->gy);   // one 8-wave / two 4-wave blocks per CU
+    const int stages = pl->M / 16;
+    if (splits > stages) splits = stages;
+    if (splits < 1) splits = 1;
+    pl->mps = ceil_div(stages, splits) * 16;
+    pl->splits = ceil_div(pl->M, pl->mps);
+    plan_groups(pl);
+}
+
 // the Winograd-domain kernel: 3x3 / s1 / p1 on an even same-size grid, 64-channel input blocks
 // from one source each, 64-channel output blocks, the 6-product arithmetic, byte offsets of the
 // (shifted) sources and of dZ under 2^31; PU_WINO_WGRAD=0 keeps the direct kernels (A/B runs)
@@ -1874,14 +1807,8 @@ static int plan_wgrad(const pu_wgrad_args* a, WgradPlan* pl) {
     PU_REQUIRE(a->dweight, "pu_wgrad: dweight missing");
     PU_REQUIRE(a->math >= 0 && a->math <= 2, "pu_wgrad: math %d", a->math);
     PU_REQUIRE(a->math != 2 || stem_wgrad_ok(a), "pu_wgrad: math 2 (bf16 rows) is the single-channel stem only");
-    const long long M = (long long)a->batch * a->out_h * a->out_w;
-    PU_REQUIRE(M < (1LL << 31), "pu_wgrad: too many pixels");
-    pl->M = (int)M;
-    pl->C = a->c0 + a->c1;
-    pl->K = a->kh * a->kw * pl->C;
-    pl->Nr = a->n + (a->bias_mode == 2 ? 1 : 0);
-    pl->Kc = pl->K + (a->bias_mode == 1 ? 1 : 0);
-    pl->Kcp = (pl->Kc + 3) / 4 * 4;
+    if (int st = plan_dims(a, pl, "pu_wgrad")) return st;
+    const long long M = pl->M;
     pl->qvec = (a->c0 % 4 == 0) && (a->c1 % 4 == 0);
     pl->small = small_wgrad_ok(a);
     pl->stem = stem_wgrad_ok(a);
@@ -1954,20 +1881,7 @@ static int plan_wgrad(const pu_wgrad_args* a, WgradPlan* pl) {
     if (a->math == 1 && pl->dma && a->kh == 3 && a->kw == 3 && a->stride == 1 && a->pad == 1 &&
         a->in_h == a->out_h && a->in_w == a->out_w && a->out_w % 16 == 0 && a->c0 % 64 == 0 && a->c1 % 64 == 0 &&
         a->n % 64 == 0 && a->bias_mode != 2 && (long long)a->batch * a->in_h * a->in_w * (pl->C) < (1LL << 31)) {
-        pl->halo = true;
-        pl->nt = a->n % 128 == 0 ? 2 : 1;    // 128 output channels per block when they divide
-        pl->BN = 64 * pl->nt;
-        pl->BK = 9 * 64;
-        const int tiles = (pl->C / 64) * (a->n / pl->BN);
-        int splits = (pl->nt == 2 ? 256 : 512) / tiles;   // one 8-wave / two 4-wave blocks per CU
-        const int stages = (int)(M / 16);
-        if (splits > stages) splits = stages;
-        if (splits < 1) splits = 1;
-        pl->mps = ceil_div(stages, splits) * 16;
-        pl->splits = ceil_div((int)M, pl->mps);
-        pl->gx = pl->C / 64;
-        pl->gy = a->n / pl->BN;
-        plan_groups(pl);
+        plan_halo(a, pl);
         return PU_OK;
     }
     pl->gx = ceil_div(ext_k, pl->BK);
@@ -2392,123 +2306,69 @@ __global__ __launch_bounds__(256) void wgrad_reduce_wide_kernel(const float* __r
     __shared__ double part[WR_S][WR_E];
     const int quad = threadIdx.x & 3, sl = threadIdx.x >> 2;
     const long long idx0 = (long long)blockIdx.x * WR_E + 4 * quad;
-    double a[4][4] = {};
-    if (idx0 < total) {                               // total % 4 == 0 (Kcp % 4 == 0)
-        const float* sp = slab + idx0;
-        int z = sl;
-        for (; z + 3 * WR_S < splits; z += 4 * WR_S) {
-            f32x4 v[4];
+    f64x4 a = {};
+    if (idx0 < total)                                 // whole quads: total % 4 == 0
+        a = sum_chains<4>(reinterpret_cast<const f32x4*>(slab + (long long)sl * total + idx0),
+                          (splits - sl + WR_S - 1) / WR_S, WR_S * (total >> 2));
 #pragma unroll
-            for (int c = 0; c < 4; ++c) v[c] = *reinterpret_cast<const f32x4*>(sp + (long long)(z + c * WR_S) * total);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a[c][e] += (double)v[c][e];
-        }
-        for (; z < splits; z += WR_S) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(sp + (long long)z * total);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a[0][e] += (double)v[e];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) part[sl][4 * quad + e] = (a[0][e] + a[1][e]) + (a[2][e] + a[3][e]);
+    for (int e = 0; e < 4; ++e) part[sl][4 * quad + e] = a[e];
     __syncthreads();
     if (threadIdx.x >= WR_E) return;
     const long long idx = (long long)blockIdx.x * WR_E + threadIdx.x;
     if (idx >= total) return;
     double sum = 0.0;
     for (int l = 0; l < WR_S; ++l) sum += part[l][threadIdx.x];
-    const float v = (float)sum;
     const int n = (int)(idx / Kcp), k = (int)(idx - (long long)n * Kcp);
     if (n >= N) return;
-    if (k < K) {
-        const int tap = k / C, ch = k - tap * C;
-        const int r = tap / kw, ss = tap - r * kw;
-        float* o = dw + (((long long)n * C + ch) * kh + r) * kw + ss;
-        *o = accumulate ? *o + v : v;
-    } else if (bias_mode == 1 && k == K) {
-        db[n] = accumulate ? db[n] + v : v;
+    store_oihw(n, k, (float)sum, K, C, kh, kw, bias_mode, dw, db, accumulate);
+}
+
+// the transposed (coalesced float4 stores) or the quad (scattered stores) finisher over `count`
+// partials: the fp32 slab's splits, or the fp64 partials of wgrad_sum_splits4_kernel
+template <typename T>
+static void launch_finisher(bool transposed, const T* part, int count, const WgradPlan& pl, const pu_wgrad_args* a,
+                            hipStream_t s) {
+    const int taps = a->kh * a->kw;
+    if (transposed) {
+        hipLaunchKernelGGL(wgrad_finish_t_kernel<T>, dim3((unsigned)ceil_div(pl.C, 256), (unsigned)a->n),
+                           dim3((unsigned)(64 * taps)), 0, s, part, count, pl.Nr, pl.Kcp, pl.K, pl.C, taps, a->bias_mode,
+                           a->dweight, a->dbias, a->accumulate);
+        return;
     }
+    const long long threads = (long long)pl.Nr * pl.Kcp / 4 + (a->bias_mode == 2 ? pl.C : 0);
+    hipLaunchKernelGGL(wgrad_finish4_kernel<T>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, part, count,
+                       pl.Nr, pl.Kcp, a->n, pl.K, pl.C, a->kh, a->kw, a->bias_mode, a->dweight, a->dbias, a->accumulate);
 }
 
 // phase 2 of every weight-gradient path: fixed-order fp64 reduction of the split partials and
-// the scatter into PyTorch's [n][c][kh][kw] (+ bias)
-// The one-launch wide reduction also takes the non-Winograd plans whose slab rows are short
+// the store into PyTorch's [n][c][kh][kw] (+ bias).
+// The one-launch wide reduction takes the direct small-channel / stem / pointwise plans (up to
+// 1024 splits of a few-thousand-entry slab) and the other non-Winograd plans whose slabs are short
 // (Nr x Kcp <= WR_WIDE_MAX entries: C4 / C5's 32-channel weight gradients, 9216 entries over
 // hundreds of splits), where the grouped form is two latency-bound launches: C5 +0.8 %, C4 +0.7 %
-// (`r06_experiments/wgrad_reduce_wide_ab.txt`).  Long rows (C2 / C3, >= 32K entries) keep the
-// grouped form: the wide one took C3's bf16 reductions from 0.36 to 1.39 ms per step.
-// PU_WR_WIDE (A/B runs): 0 = small / stem / pointwise plans only (the round-6 form), 2 = every plan.
+// (`r06_experiments/wgrad_reduce_wide_ab.txt`).  Long slabs (C2 / C3, >= 32K entries) keep the
+// grouped form: the wide one took C3's bf16 reductions from 0.36 to 1.39 ms per step, and the
+// Winograd-domain kernel's 64-256 splits from 0.32 to 0.37 ms per C2 step.
 // The split partials are summed in fp64 either way, in a different fixed order.
 constexpr long long WR_WIDE_MAX = 16384;
-static int wr_wide_mode() {
-    static const int m = [] {
-        const char* e = getenv("PU_WR_WIDE");
-        return e ? atoi(e) : 1;
-    }();
-    return m;
-}
 
 static int wgrad_reduce(const WgradPlan& pl, const pu_wgrad_args* a, void* workspace, hipStream_t s) {
     const long long total = (long long)pl.Nr * pl.Kcp;
-    const long long threads = total + (a->bias_mode == 2 ? pl.C : 0);
-    const dim3 fgrid((unsigned)((threads + 255) / 256));
-    const int taps = a->kh * a->kw;
-    // one launch for up to 1024 splits of a few-thousand-entry slab (the direct small-channel /
-    // stem kernels; measured slower than the two-pass grouped form on the Winograd-domain
-    // kernel's 64-256 splits: 0.37 vs 0.32 ms per C2 step)
-    const bool wide = pl.small || pl.stem || pl.pw || (wr_wide_mode() == 1 && !pl.wino && total <= WR_WIDE_MAX) ||
-                      wr_wide_mode() == 2;
-    if (wide && a->bias_mode != 2 && pl.Kcp % 4 == 0) {
+    const float* slab = (const float*)workspace;
+    if ((pl.small || pl.stem || pl.pw || (!pl.wino && total <= WR_WIDE_MAX)) && a->bias_mode != 2) {
         hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)ceil_div(total, (long long)WR_E)), dim3(256), 0, s,
-                           (const float*)workspace, pl.splits, total, a->n, pl.Kcp, pl.K, pl.C, a->kh, a->kw,
-                           a->bias_mode, a->dweight, a->dbias, a->accumulate);
+                           slab, pl.splits, total, a->n, pl.Kcp, pl.K, pl.C, a->kh, a->kw, a->bias_mode, a->dweight,
+                           a->dbias, a->accumulate);
         return check_launch("pu_wgrad (reduce)");
     }
-    if (a->bias_mode != 2 && taps <= 9 && pl.C % 4 == 0 && pl.Kcp % 4 == 0 && ((uintptr_t)a->dweight & 15) == 0) {
-        const dim3 tgrid((unsigned)ceil_div(pl.C, 256), (unsigned)a->n);
-        const dim3 tblock((unsigned)(64 * taps));
-        if (pl.G == 1) {
-            hipLaunchKernelGGL(wgrad_finish_t_kernel<float>, tgrid, tblock, 0, s, (const float*)workspace, pl.splits,
-                               pl.Nr, pl.Kcp, pl.K, pl.C, taps, a->bias_mode, a->dweight, a->dbias, a->accumulate);
-        } else {
-            double* part = (double*)((char*)workspace + ((pl.slab_bytes() + 255) / 256) * 256);
-            hipLaunchKernelGGL(wgrad_sum_splits4_kernel, dim3((unsigned)((total / 4 + 255) / 256), pl.G), dim3(256), 0,
-                               s, (const float*)workspace, pl.splits, total, pl.G, part);
-            hipLaunchKernelGGL(wgrad_finish_t_kernel<double>, tgrid, tblock, 0, s, (const double*)part, pl.G, pl.Nr,
-                               pl.Kcp, pl.K, pl.C, taps, a->bias_mode, a->dweight, a->dbias, a->accumulate);
-        }
-        return check_launch("pu_wgrad (reduce)");
-    }
-    if (pl.Kcp % 4 == 0) {
-        const long long threads4 = total / 4 + (a->bias_mode == 2 ? pl.C : 0);
-        const dim3 grid4((unsigned)((threads4 + 255) / 256));
-        if (pl.G == 1) {
-            hipLaunchKernelGGL(wgrad_finish4_kernel<float>, grid4, dim3(256), 0, s, (const float*)workspace,
-                               pl.splits, pl.Nr, pl.Kcp, a->n, pl.K, pl.C, a->kh, a->kw, a->bias_mode, a->dweight,
-                               a->dbias, a->accumulate);
-        } else {
-            double* part = (double*)((char*)workspace + ((pl.slab_bytes() + 255) / 256) * 256);
-            hipLaunchKernelGGL(wgrad_sum_splits4_kernel, dim3((unsigned)((total / 4 + 255) / 256), pl.G), dim3(256), 0,
-                               s, (const float*)workspace, pl.splits, total, pl.G, part);
-            hipLaunchKernelGGL(wgrad_finish4_kernel<double>, grid4, dim3(256), 0, s, (const double*)part, pl.G,
-                               pl.Nr, pl.Kcp, a->n, pl.K, pl.C, a->kh, a->kw, a->bias_mode, a->dweight, a->dbias,
-                               a->accumulate);
-        }
-        return check_launch("pu_wgrad (reduce)");
-    }
-    if (pl.G == 1) {
-        hipLaunchKernelGGL(wgrad_finish_kernel<float>, fgrid, dim3(256), 0, s, (const float*)workspace, pl.splits,
-                           pl.Nr, pl.Kcp, a->n, pl.K, pl.C, a->kh, a->kw, a->bias_mode, a->dweight, a->dbias,
-                           a->accumulate);
-    } else {
+    const bool transposed = a->bias_mode != 2 && a->kh * a->kw <= 9 && pl.C % 4 == 0 && ((uintptr_t)a->dweight & 15) == 0;
+    if (pl.G > 1) {
         double* part = (double*)((char*)workspace + ((pl.slab_bytes() + 255) / 256) * 256);
-        hipLaunchKernelGGL(wgrad_sum_splits_kernel, dim3((unsigned)((total + 255) / 256), pl.G), dim3(256), 0, s,
-                           (const float*)workspace, pl.splits, total, pl.G, part);
-        hipLaunchKernelGGL(wgrad_finish_kernel<double>, fgrid, dim3(256), 0, s, (const double*)part, pl.G, pl.Nr,
-                           pl.Kcp, a->n, pl.K, pl.C, a->kh, a->kw, a->bias_mode, a->dweight, a->dbias,
-                           a->accumulate);
+        hipLaunchKernelGGL(wgrad_sum_splits4_kernel, dim3((unsigned)((total / 4 + 255) / 256), pl.G), dim3(256), 0, s,
+                           slab, pl.splits, total, pl.G, part);
+        launch_finisher(transposed, (const double*)part, pl.G, pl, a, s);
+    } else {
+        launch_finisher(transposed, slab, pl.splits, pl, a, s);
     }
     return check_launch("pu_wgrad (reduce)");
 }
@@ -2523,30 +2383,14 @@ static int plan_wgrad_bf16(const pu_wgrad_args* a, WgradPlan* pl) {
                "pu_wgrad_bf16: n (%d) and channel counts (%d, %d) must be multiples of 8", a->n, a->c0, a->c1);
     PU_REQUIRE(a->bias_mode >= 0 && a->bias_mode <= 2 && (a->bias_mode == 0 || a->dbias) && a->dweight, "pu_wgrad_bf16: outputs");
     PU_REQUIRE((((uintptr_t)a->rows | (uintptr_t)a->src0 | (uintptr_t)a->src1) & 15) == 0, "pu_wgrad_bf16: 16-byte alignment");
-    const long long M = (long long)a->batch * a->out_h * a->out_w;
-    PU_REQUIRE(M < (1LL << 31), "pu_wgrad_bf16: too many pixels");
-    pl->M = (int)M;
-    pl->C = a->c0 + a->c1;
-    pl->K = a->kh * a->kw * pl->C;
-    pl->Nr = a->n + (a->bias_mode == 2 ? 1 : 0);
-    pl->Kc = pl->K + (a->bias_mode == 1 ? 1 : 0);
-    pl->Kcp = (pl->Kc + 3) / 4 * 4;
+    if (int st = plan_dims(a, pl, "pu_wgrad_bf16")) return st;
+    const long long M = pl->M;
     pl->qvec = true; pl->dma = true; pl->small = false; pl->stem = false;
-    pl->halo = a->kh == 3 && a->kw == 3 && a->stride == 1 && a->pad == 1 && a->in_h == a->out_h &&
-               a->in_w == a->out_w && a->out_w % 16 == 0 && a->c0 % 64 == 0 && a->c1 % 64 == 0 && a->n % 64 == 0 &&
-               a->bias_mode != 2 && M * pl->C < (1LL << 31);
-    if (pl->halo) {                   // wgrad_halo_bf16_kernel: 64 NT x 64 x 9-tap tiles, 512 NT-thread blocks
-        pl->nt = a->n % 128 == 0 ? 2 : 1;
-        pl->BN = 64 * pl->nt; pl->BK = 9 * 64;
-        pl->gx = pl->C / 64;
-        pl->gy = a->n / pl->BN;
-        const int stages = (int)(M / 16);
-        int splits = (pl->nt == 2 ? 256 : 512) / (pl->gx * pl->gy);   // one 8-wave / two 4-wave blocks per CU
-        if (splits > stages) splits = stages;
-        if (splits < 1) splits = 1;
-        pl->mps = ceil_div(stages, splits) * 16;
-        pl->splits = ceil_div((int)M, pl->mps);
-        plan_groups(pl);
+    pl->halo = false;
+    if (a->kh == 3 && a->kw == 3 && a->stride == 1 && a->pad == 1 && a->in_h == a->out_h &&
+        a->in_w == a->out_w && a->out_w % 16 == 0 && a->c0 % 64 == 0 && a->c1 % 64 == 0 && a->n % 64 == 0 &&
+        a->bias_mode != 2 && M * pl->C < (1LL << 31)) {
+        plan_halo(a, pl);
         return PU_OK;
     }
     pl->BN = WB_W; pl->BK = WB_W;

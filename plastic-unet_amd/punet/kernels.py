@@ -309,6 +309,16 @@ def _igemm_bf16(L, a, batch, out_hw, k, c0, c1, n, dst0):
         check(L.pu_conv_igemm_bf16(ctypes.byref(a), _stream()), "pu_conv_igemm_bf16")
 
 
+def wgrad_args(*, batch, in_hw, out_hw, k, stride, pad, rows, n, src0, c0, dweight, src1=None, c1=0,
+               bias_mode=0, dbias=None, accumulate=False, math=None):
+    """The pu_wgrad_args of one kxk weight gradient.  rows, src0, src1, dweight and dbias are device
+    addresses (None: absent); math None is the fp32 arithmetic PU_FP32_MATH selects."""
+    if math is None:
+        math = 1 if _FP32_MATH == "split6" else 0
+    return WgradArgs(batch, in_hw[0], in_hw[1], out_hw[0], out_hw[1], k, k, stride, pad,
+                     rows, n, src0, c0, src1, c1, bias_mode, dweight, dbias, 1 if accumulate else 0, math)
+
+
 def wgrad(*, batch, in_hw, out_hw, k, stride, pad, rows, n, src0, c0, dweight, src1=None, c1=0,
           bias_mode=0, dbias=None, accumulate=False):
     """pu_wgrad: split-K weight (+bias) gradient into PyTorch's [n][c][k][k] layout (fp32, or
@@ -319,9 +329,9 @@ def wgrad(*, batch, in_hw, out_hw, k, stride, pad, rows, n, src0, c0, dweight, s
     for t, nm in ((rows, "rows"), (src0, "src0"), (src1, "src1")):
         _req(t, nm, BF16 if (stem_bf16 and nm == "rows") else dt)
     _req(dweight, "dweight"); _req(dbias, "dbias")
-    a = WgradArgs(batch, in_hw[0], in_hw[1], out_hw[0], out_hw[1], k, k, stride, pad,
-                  _p(rows), n, _p(src0), c0, _p(src1), c1, bias_mode, _p(dweight), _p(dbias),
-                  1 if accumulate else 0, 2 if stem_bf16 else (1 if (dt != BF16 and _FP32_MATH == "split6") else 0))
+    a = wgrad_args(batch=batch, in_hw=in_hw, out_hw=out_hw, k=k, stride=stride, pad=pad, rows=_p(rows), n=n,
+                   src0=_p(src0), c0=c0, src1=_p(src1), c1=c1, bias_mode=bias_mode, dweight=_p(dweight),
+                   dbias=_p(dbias), accumulate=accumulate, math=2 if stem_bf16 else 0 if dt == BF16 else None)
     L = lib()
     if dt == BF16:
         nbytes = L.pu_wgrad_bf16_workspace_bytes(ctypes.byref(a))
@@ -364,9 +374,8 @@ def wgrad_kind(*, batch, hw, n, c0, c1=0, k=3):
     """Which kernel pu_wgrad takes for an fp32 kxk/s1 same-size ('same' padding) weight gradient
     (pu_wgrad_tile's loader kind: 1 float4 GEMM, 2 small-channel direct, 3 halo, 4 stem,
     5 Winograd-domain, 6 pointwise)."""
-    a = WgradArgs(batch, hw[0], hw[1], hw[0], hw[1], k, k, 1, (k - 1) // 2, 16, n, 16, c0, 16 if c1 else None, c1, 1,
-                  16, 16,
-                  0, 1 if _FP32_MATH == "split6" else 0)
+    a = wgrad_args(batch=batch, in_hw=hw, out_hw=hw, k=k, stride=1, pad=(k - 1) // 2, rows=16, n=n, src0=16, c0=c0,
+                   src1=16 if c1 else None, c1=c1, bias_mode=1, dweight=16, dbias=16)
     bn, bk, qv, sp = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     check(lib().pu_wgrad_tile(ctypes.byref(a), ctypes.byref(bn), ctypes.byref(bk), ctypes.byref(qv), ctypes.byref(sp)),
           "pu_wgrad_tile")

@@ -74,6 +74,39 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t x, const FastDiv& f) {
 
 inline int ceil_div(long long a, long long b) { return int((a + b - 1) / b); }
 
+// ------------------------------------- tile and split-K choice of the tiled implicit-GEMM kernels
+// (igemm.hip's igemm_kernel / igemm_dma_kernel, igemm_bf16.hip's igemm_bf16_kernel)
+inline int blocks_for(long long M, int N, int bm, int bn) { return ceil_div(M, bm) * ceil_div(N, bn); }
+
+// the largest tile that still gives >= ~2 blocks per CU (256 CUs)
+inline void choose_tile(long long M, int N, int* bm, int* bn) {
+    const int target = 480;
+    if (N <= 64) {
+        if (blocks_for(M, N, 256, 64) >= target) { *bm = 256; *bn = 64; }
+        else if (blocks_for(M, N, 128, 64) >= target) { *bm = 128; *bn = 64; }
+        else { *bm = 64; *bn = 64; }
+    } else {
+        if (blocks_for(M, N, 128, 128) >= target) { *bm = 128; *bn = 128; }
+        else if (blocks_for(M, N, 128, 64) >= target) { *bm = 128; *bn = 64; }
+        else { *bm = 64; *bn = 64; }
+    }
+}
+
+// When the M x N tile grid fills fewer than the resident block slots of the chip (256 CUs x blocks
+// per CU of the tile), split the k_pad / bk K stages so that it does, keeping >= min_stages stages
+// per split.
+inline void plan_split(int k_pad, int bk, int min_stages, long long M, int N, int bm, int bn, int* ksplit, int* t_per) {
+    const int T = k_pad / bk;
+    *ksplit = 1;
+    *t_per = T;
+    const int occ = (bm == 256) ? 2 : (bm == 128 && bn == 128) ? 3 : 4;   // LDS-limited (3-deep ring)
+    int ks = (256 * occ) / blocks_for(M, N, bm, bn);
+    if (ks > T / min_stages) ks = T / min_stages;
+    if (ks < 2) return;
+    *t_per = ceil_div(T, ks);
+    *ksplit = ceil_div(T, *t_per);
+}
+
 // 4-term dot product as an explicit fma chain (v0 w0 first): the 1x1 outconv's per-lane sum, shared
 // by outconv_fwd_kernel and the fused head so both produce bit-identical logits
 template <typename V>

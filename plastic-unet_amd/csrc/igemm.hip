@@ -14,11 +14,6 @@
 #include "conv_common.h"
 #include <type_traits>
 
-
-#ifndef PU_EPI_BATCH
-#define PU_EPI_BATCH 1   // 0: every output through epi_store4 (A/B builds)
-#endif
-
 namespace pu {
 
 
@@ -212,7 +207,7 @@ __device__ __forceinline__ void epilogue(const IgemmParams& p, f32x16 (&acc)[BM 
                                          int n_blk, int wm, int wn, int lr, int lh) {
     constexpr int FM = BM / WM / 32;
     constexpr int FN = BN / WN / 32;
-    if constexpr (BATCH && PU_EPI_BATCH) {
+    if constexpr (BATCH) {
         // 32-column fragments never straddle n0; every destination byte offset fits 31 bits
         if (p.vec_epi && !(p.flags & (PU_EPI_SHUFFLE2 | PU_EPI_ACCUM)) && !p.resid && !p.cscale && p.n0 % 32 == 0 &&
             p.N % 32 == 0 && (long long)p.M * p.N < (1LL << 29)) {
@@ -1319,32 +1314,12 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const IgemmParams p) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-struct TileCfg {
-    int bm, bn;
-};
-
 template <int BM, int BN, int WM, int WN>
 static void launch_mode(int mode, const IgemmParams& p, dim3 grid, hipStream_t s) {
     switch (mode) {
         case LOAD_CHUNK16: hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, LOAD_CHUNK16>), grid, dim3(256), 0, s, p); break;
         case LOAD_VEC4: hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, LOAD_VEC4>), grid, dim3(256), 0, s, p); break;
         default: hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, LOAD_SCALAR>), grid, dim3(256), 0, s, p); break;
-    }
-}
-
-static int blocks_for(long long M, int N, int bm, int bn) { return ceil_div(M, bm) * ceil_div(N, bn); }
-
-// tile choice: the largest tile that still gives >= ~2 blocks per CU (256 CUs)
-static void choose_tile(long long M, int N, int* bm, int* bn) {
-    const int target = 480;
-    if (N <= 64) {
-        if (blocks_for(M, N, 256, 64) >= target) { *bm = 256; *bn = 64; }
-        else if (blocks_for(M, N, 128, 64) >= target) { *bm = 128; *bn = 64; }
-        else { *bm = 64; *bn = 64; }
-    } else {
-        if (blocks_for(M, N, 128, 128) >= target) { *bm = 128; *bn = 128; }
-        else if (blocks_for(M, N, 128, 64) >= target) { *bm = 128; *bn = 64; }
-        else { *bm = 64; *bn = 64; }
     }
 }
 
@@ -1361,23 +1336,6 @@ static bool vec_epilogue(const pu_conv_args* a) {
                          (uintptr_t)a->bias | ((a->flags & PU_EPI_RESID) ? (uintptr_t)a->resid : 0);
     // SHUFFLE2: 4 consecutive n stay inside one (i,j) block only when co = n/4 is a multiple of 4
     return (a->n % 4 == 0) && (n0 % 4 == 0) && (al & 15) == 0 && (!shuffle || (a->n / 4) % 4 == 0);
-}
-
-// Split-K plan: when the M x N tile grid fills fewer than the resident block slots of the chip
-// (256 CUs x blocks per CU of the tile), split the K stages so that it does, keeping >= 8 stages
-// (128 k) per split.  Only the direct-to-LDS kernel splits.
-static void plan_split(const pu_conv_args* a, long long M, int bm, int bn, int* ksplit, int* t_per) {
-    const int T = a->k_pad / IG_BK;
-    *ksplit = 1;
-    *t_per = T;
-    if (choose_mode(a->c0, a->c1) != LOAD_CHUNK16 || !vec_epilogue(a)) return;
-    const int occ = (bm == 256) ? 2 : (bm == 128 && bn == 128) ? 3 : 4;   // LDS-limited (3-deep ring)
-    const int blocks = blocks_for(M, a->n, bm, bn);
-    int ks = (256 * occ) / blocks;
-    if (ks > T / 8) ks = T / 8;
-    if (ks < 2) return;
-    *t_per = ceil_div(T, ks);
-    *ksplit = ceil_div(T, *t_per);
 }
 
 // Tile / split plan of one call.  The 6-product kernel does 6x the MFMA work per K stage of the
@@ -1399,13 +1357,17 @@ static bool lean_ok(const pu_conv_args* a) {
     return true;
 }
 static void plan_tiles(const pu_conv_args* a, long long M, int* bm, int* bn, int* ksplit, int* t_per) {
-    if (!uses_x6(a)) {
-        choose_tile(M, a->n, bm, bn);
-        plan_split(a, M, *bm, *bn, ksplit, t_per);
-        return;
-    }
     const int N = a->n;
     const int T = a->k_pad / IG_BK;
+    if (!uses_x6(a)) {
+        // only the direct-to-LDS kernel splits (common.h plan_split): >= 8 stages (128 k) per split
+        choose_tile(M, N, bm, bn);
+        *ksplit = 1;
+        *t_per = T;
+        if (choose_mode(a->c0, a->c1) == LOAD_CHUNK16 && vec_epilogue(a))
+            plan_split(a->k_pad, IG_BK, 8, M, N, *bm, *bn, ksplit, t_per);
+        return;
+    }
     int target = 512;                 // ~2 resident blocks per CU (4-wave tiles)
     if (N <= 32 && lean_ok(a)) {      // 32-channel layers (C4/C5 levels): no half-empty 64-wide tiles
         *bn = 32;
@@ -1473,8 +1435,70 @@ static bool uses_x6(const pu_conv_args* a) {
     return a->weight6 && choose_mode(a->c0, a->c1) == LOAD_CHUNK16 && !small_conv_ok(a);
 }
 
-static size_t split_bytes(long long M, int n, int ksplit) {
-    return ksplit > 1 ? (size_t)ksplit * (size_t)M * (size_t)n * sizeof(float) : 0;
+// What one call runs: the kernel, the tile and loader mode pu_conv_igemm_tile reports, its K split
+// and the scratch the planned split needs.  pu_conv_igemm launches the plan, the two queries report
+// it.
+enum { CK_STEM, CK_1X1, CK_SMALLX6, CK_DIRECT, CK_WINO, CK_X6_LEAN, CK_X6, CK_DMA, CK_LOADER };
+struct ConvPlan {
+    int kind, bm, bn;
+    int mode;               // 0 chunk16, 1 vec4, 2 scalar, 3 direct, 4 x6, 5 stem, 6 wino, 7 x6s
+    int ksplit, t_per;      // the split this call runs: 1 without the scratch the plan asks for
+    size_t ws_bytes;        // fp32 partial tiles of the planned split (0: the plan does not split)
+};
+
+// The dispatch ladder: stem, 1x1 small, smallx6, small-channel direct, Winograd, then the tiled
+// kernels (x6 lean, x6, DMA, loader modes) on plan_tiles' tile.  Reads a as it is: the launcher
+// validates before it plans, the queries do not.
+static ConvPlan plan_conv(const pu_conv_args* a, long long M) {
+    ConvPlan pl;
+    pl.bn = a->n;
+    pl.ksplit = 1;
+    pl.t_per = a->k_pad / IG_BK;
+    pl.ws_bytes = 0;
+    const bool vec = vec_epilogue(a);
+    if (stem_conv_ok(a)) {                  // tile ST_TH x ST_TW pixels
+        pl.kind = CK_STEM;
+        pl.mode = 5;
+        pl.bm = ST_TH * ST_TW;
+        return pl;
+    }
+    if (conv1x1_small_ok(a)) {              // one pixel per thread
+        pl.kind = CK_1X1;
+        pl.mode = 3;
+        pl.bm = 256;
+        return pl;
+    }
+    if (smallx6_ok(a, vec)) {               // 16 x 32 pixels x n (stride 2: 4 x 32)
+        pl.kind = CK_SMALLX6;
+        pl.mode = 7;
+        pl.bm = a->stride == 2 ? 128 : a->kh == 2 ? 256 : 512;
+        return pl;
+    }
+    if (small_conv_ok(a)) {                 // tile SC_TH x SC_TW pixels
+        pl.kind = CK_DIRECT;
+        pl.mode = 3;
+        pl.bm = SC_TH * SC_TW;
+        return pl;
+    }
+    if (wino_ok(a, vec)) {                  // 64 tiles (256 pixels) x 64 channels, or 32 tiles x 128 channels
+        pl.kind = CK_WINO;
+        pl.mode = 6;
+        pl.bn = wino_item_channels(a);
+        pl.bm = pl.bn == 64 ? 256 : 128;
+        pl.ws_bytes = wino_workspace_bytes(a);
+        if (pl.ws_bytes) pl.ksplit = (int)(pl.ws_bytes / ((size_t)M * a->n * sizeof(float)));
+    } else {
+        plan_tiles(a, M, &pl.bm, &pl.bn, &pl.ksplit, &pl.t_per);
+        const int loader = choose_mode(a->c0, a->c1);
+        pl.kind = uses_x6(a) ? (lean_ok(a) ? CK_X6_LEAN : CK_X6) : loader == LOAD_CHUNK16 ? CK_DMA : CK_LOADER;
+        pl.mode = uses_x6(a) ? 4 : loader;
+        if (pl.ksplit > 1) pl.ws_bytes = (size_t)pl.ksplit * (size_t)M * (size_t)a->n * sizeof(float);
+    }
+    if (pl.ksplit > 1 && (!a->workspace || a->ws_bytes < pl.ws_bytes)) {     // no or too little scratch: unsplit
+        pl.ksplit = 1;
+        pl.t_per = a->k_pad / IG_BK;
+    }
+    return pl;
 }
 
 }  // namespace pu
@@ -1544,121 +1568,117 @@ extern "C" int pu_conv_igemm(const pu_conv_args* a, void* stream) {
     }
     PU_REQUIRE(((uintptr_t)a->weight & 15) == 0, "pu_conv_igemm: weight must be 16-byte aligned");
 
-    hipStream_t s = as_stream(stream);
-    const int N = a->n;
-    if (a->flags & PU_EPI_OUT_BF16) {
+    const bool out_bf16 = a->flags & PU_EPI_OUT_BF16;
+    if (out_bf16) {
         PU_REQUIRE(stem_conv_ok(a) && !a->mask0 && !a->mask1 && !a->resid && !a->chan_scale && a->n0 == a->n &&
                        !(a->flags & (PU_EPI_ACCUM | PU_EPI_SHUFFLE2)) && ((uintptr_t)a->dst0 & 7) == 0,
                    "pu_conv_igemm: PU_EPI_OUT_BF16 is the single-channel stem conv only (c0 1, 3x3/s1/p1, n 8/16/32/64, "
                    "no mask/resid/accum/shuffle/chan_scale, 8-byte aligned dst0)");
-        p.ksplit = 1;
-        const dim3 sgrid((unsigned)(((a->out_w + ST_TW - 1) / ST_TW) * ((a->out_h + ST_TH - 1) / ST_TH) * a->batch));
-        if (N == 64) hipLaunchKernelGGL((stem_conv_kernel<64, true>), sgrid, dim3(256), 0, s, p);
-        else if (N == 32) hipLaunchKernelGGL((stem_conv_kernel<32, true>), sgrid, dim3(256), 0, s, p);
-        else if (N == 16) hipLaunchKernelGGL((stem_conv_kernel<16, true>), sgrid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((stem_conv_kernel<8, true>), sgrid, dim3(256), 0, s, p);
-        return check_launch("pu_conv_igemm (stem, bf16 out)");
     }
-    if (stem_conv_ok(a)) {
-        p.ksplit = 1;
-        const dim3 sgrid((unsigned)(((a->out_w + ST_TW - 1) / ST_TW) * ((a->out_h + ST_TH - 1) / ST_TH) * a->batch));
-        if (N == 64) hipLaunchKernelGGL((stem_conv_kernel<64>), sgrid, dim3(256), 0, s, p);
-        else if (N == 32) hipLaunchKernelGGL((stem_conv_kernel<32>), sgrid, dim3(256), 0, s, p);
-        else if (N == 16) hipLaunchKernelGGL((stem_conv_kernel<16>), sgrid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((stem_conv_kernel<8>), sgrid, dim3(256), 0, s, p);
-        return check_launch("pu_conv_igemm (stem)");
-    }
-    if (conv1x1_small_ok(a)) {
-        p.ksplit = 1;
-        const dim3 g1((unsigned)(M / 256 + 1 < 8192 ? M / 256 + 1 : 8192));
-        if (C == 4 && N == 8) hipLaunchKernelGGL((conv1x1_small_kernel<4, 8>), g1, dim3(256), 0, s, p);
-        else if (C == 4) hipLaunchKernelGGL((conv1x1_small_kernel<4, 16>), g1, dim3(256), 0, s, p);
-        else if (N == 8) hipLaunchKernelGGL((conv1x1_small_kernel<8, 8>), g1, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((conv1x1_small_kernel<8, 16>), g1, dim3(256), 0, s, p);
-        return check_launch("pu_conv_igemm (1x1 small-channel)");
-    }
-    if (smallx6_ok(a, p.vec_epi)) {
-        p.ksplit = 1;
-        return smallx6_launch(a, p, s);
-    }
-    if (small_conv_ok(a)) {
-        p.ksplit = 1;
-        const dim3 sgrid((unsigned)(((a->out_w + SC_TW - 1) / SC_TW) * ((a->out_h + SC_TH - 1) / SC_TH) * a->batch));
-#define PU_SC(C_, N_) if (C == C_ && N == N_) hipLaunchKernelGGL((smallconv_kernel<C_, N_>), sgrid, dim3(256), 0, s, p)
-        PU_SC(1, 8); else PU_SC(1, 16); else PU_SC(4, 8); else PU_SC(4, 16); else PU_SC(8, 8); else PU_SC(8, 16);
-        else PU_SC(12, 8); else PU_SC(12, 16); else PU_SC(16, 8); else PU_SC(16, 16);
-        else PU_SC(4, 4); else PU_SC(8, 4); else PU_SC(16, 4);
-#undef PU_SC
-        return check_launch("pu_conv_igemm (small-channel)");
-    }
-    if (wino_ok(a, p.vec_epi)) {
+    const ConvPlan pl = plan_conv(a, M);
+    if (pl.kind == CK_WINO || pl.kind == CK_X6_LEAN || pl.kind == CK_X6) {
         PU_REQUIRE(((uintptr_t)a->weight6 & 15) == 0, "pu_conv_igemm: weight6 must be 16-byte aligned");
-        p.gn = N / 64;
-        p.part = (float*)a->workspace;
-        p.ksplit = wino_launch(a, p, s);
-        if (p.ksplit > 1) {
-            const long long tot = M * (N / 4);
-            hipLaunchKernelGGL(igemm_splitk_epilogue_kernel, dim3((unsigned)ceil_div(tot, 256)), dim3(256), 0, s, p);
-        }
-        return check_launch("pu_conv_igemm (winograd x6)");
     }
-    int bm, bn;
-    plan_tiles(a, M, &bm, &bn, &p.ksplit, &p.t_per);
-    p.gn = ceil_div(N, bn);
-    if (p.ksplit > 1 && (!a->workspace || a->ws_bytes < split_bytes(M, N, p.ksplit))) {
-        p.ksplit = 1;                       // no scratch: unsplit
-        p.t_per = a->k_pad / IG_BK;
-    }
+    hipStream_t s = as_stream(stream);
+    const int N = a->n;
+    const int bm = pl.bm, bn = pl.bn;
+    p.ksplit = pl.ksplit;
+    p.t_per = pl.t_per;
     p.part = (float*)a->workspace;
-    const dim3 grid(ceil_div(M, bm) * p.gn * p.ksplit);
-    if (a->weight6 && mode == LOAD_CHUNK16) {
-        p.wt = reinterpret_cast<const float*>(a->weight6);
-        PU_REQUIRE(((uintptr_t)a->weight6 & 15) == 0, "pu_conv_igemm: weight6 must be 16-byte aligned");
-        if (lean_ok(a)) {
+    p.gn = ceil_div(N, bn);
+    const dim3 grid(ceil_div(M, bm) * p.gn * p.ksplit);      // the tiled kernels' (CK_X6_LEAN ... CK_LOADER)
+    const char* what = "pu_conv_igemm";
+    switch (pl.kind) {
+        case CK_STEM: {
+            const dim3 sgrid((unsigned)(((a->out_w + ST_TW - 1) / ST_TW) * ((a->out_h + ST_TH - 1) / ST_TH) * a->batch));
+            if (out_bf16) {
+                if (N == 64) hipLaunchKernelGGL((stem_conv_kernel<64, true>), sgrid, dim3(256), 0, s, p);
+                else if (N == 32) hipLaunchKernelGGL((stem_conv_kernel<32, true>), sgrid, dim3(256), 0, s, p);
+                else if (N == 16) hipLaunchKernelGGL((stem_conv_kernel<16, true>), sgrid, dim3(256), 0, s, p);
+                else hipLaunchKernelGGL((stem_conv_kernel<8, true>), sgrid, dim3(256), 0, s, p);
+                what = "pu_conv_igemm (stem, bf16 out)";
+                break;
+            }
+            if (N == 64) hipLaunchKernelGGL((stem_conv_kernel<64>), sgrid, dim3(256), 0, s, p);
+            else if (N == 32) hipLaunchKernelGGL((stem_conv_kernel<32>), sgrid, dim3(256), 0, s, p);
+            else if (N == 16) hipLaunchKernelGGL((stem_conv_kernel<16>), sgrid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((stem_conv_kernel<8>), sgrid, dim3(256), 0, s, p);
+            what = "pu_conv_igemm (stem)";
+            break;
+        }
+        case CK_1X1: {
+            const dim3 g1((unsigned)(M / 256 + 1 < 8192 ? M / 256 + 1 : 8192));
+            if (C == 4 && N == 8) hipLaunchKernelGGL((conv1x1_small_kernel<4, 8>), g1, dim3(256), 0, s, p);
+            else if (C == 4) hipLaunchKernelGGL((conv1x1_small_kernel<4, 16>), g1, dim3(256), 0, s, p);
+            else if (N == 8) hipLaunchKernelGGL((conv1x1_small_kernel<8, 8>), g1, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((conv1x1_small_kernel<8, 16>), g1, dim3(256), 0, s, p);
+            what = "pu_conv_igemm (1x1 small-channel)";
+            break;
+        }
+        case CK_SMALLX6:
+            return smallx6_launch(a, p, s);
+        case CK_DIRECT: {
+            const dim3 sgrid((unsigned)(((a->out_w + SC_TW - 1) / SC_TW) * ((a->out_h + SC_TH - 1) / SC_TH) * a->batch));
+#define PU_SC(C_, N_) if (C == C_ && N == N_) hipLaunchKernelGGL((smallconv_kernel<C_, N_>), sgrid, dim3(256), 0, s, p)
+            PU_SC(1, 8); else PU_SC(1, 16); else PU_SC(4, 8); else PU_SC(4, 16); else PU_SC(8, 8); else PU_SC(8, 16);
+            else PU_SC(12, 8); else PU_SC(12, 16); else PU_SC(16, 8); else PU_SC(16, 16);
+            else PU_SC(4, 4); else PU_SC(8, 4); else PU_SC(16, 4);
+#undef PU_SC
+            what = "pu_conv_igemm (small-channel)";
+            break;
+        }
+        case CK_WINO:
+            p.gn = N / 64;
+            wino_launch(a, p, s);
+            what = "pu_conv_igemm (winograd x6)";
+            break;
+        case CK_X6_LEAN: {
+            p.wt = reinterpret_cast<const float*>(a->weight6);
             const int cg = a->cgroup / 16;
-            bool done = true;
 #define PU_XL(BM_, BN_, WM_, WN_, NW_)                                                                          \
     do {                                                                                                        \
         if (cg == 2) hipLaunchKernelGGL((igemm_x6_lean_kernel<BM_, BN_, WM_, WN_, NW_, 2>), grid, dim3(NW_ * 64), 0, s, p); \
         else hipLaunchKernelGGL((igemm_x6_lean_kernel<BM_, BN_, WM_, WN_, NW_, 1>), grid, dim3(NW_ * 64), 0, s, p); \
     } while (0)
+            // every tile plan_tiles gives a lean call is here: 256 | 128 x 32 (N <= 32), 256 | 128 x 64
+            // (N <= 64), 256 x 128 (k_pad >= 2048) or 128 x 128
             if (bm == 256 && bn == 128) PU_XL(256, 128, 8, 1, 8);
             else if (bm == 256 && bn == 64) PU_XL(256, 64, 8, 1, 8);   // 8 x 1 waves: fwd +3-4 % over 4 x 1
             else if (bm == 128 && bn == 128) PU_XL(128, 128, 4, 1, 4);
             else if (bm == 128 && bn == 64) PU_XL(128, 64, 2, 2, 4);
-            else if (bm == 256 && bn == 32) PU_XL(256, 32, 4, 1, 4);
-            else if (bm == 128 && bn == 32) PU_XL(128, 32, 4, 1, 4);
-            else done = false;
+            else if (bm == 256) PU_XL(256, 32, 4, 1, 4);
+            else PU_XL(128, 32, 4, 1, 4);
 #undef PU_XL
-            if (done) {
-                if (p.ksplit > 1) {
-                    const long long tot = M * (N / 4);
-                    hipLaunchKernelGGL(igemm_splitk_epilogue_kernel, dim3((unsigned)ceil_div(tot, 256)), dim3(256), 0, s, p);
-                }
-                return check_launch("pu_conv_igemm (x6 lean)");
-            }
+            what = "pu_conv_igemm (x6 lean)";
+            break;
         }
+        case CK_X6:
+            p.wt = reinterpret_cast<const float*>(a->weight6);
 #define PU_X6(BM_, BN_, WM_, WN_) hipLaunchKernelGGL((igemm_x6_kernel<BM_, BN_, WM_, WN_>), grid, dim3(256), 0, s, p)
-        if (bm == 256 && bn == 128)
-            hipLaunchKernelGGL((igemm_x6_kernel<256, 128, 8, 1, 8>), grid, dim3(512), 0, s, p);
-        else if (bm == 256) PU_X6(256, 64, 4, 1);
-        else if (bm == 128 && bn == 128) PU_X6(128, 128, 4, 1);
-        else PU_X6(128, 64, 2, 2);
+            if (bm == 256 && bn == 128)
+                hipLaunchKernelGGL((igemm_x6_kernel<256, 128, 8, 1, 8>), grid, dim3(512), 0, s, p);
+            else if (bm == 256) PU_X6(256, 64, 4, 1);
+            else if (bm == 128 && bn == 128) PU_X6(128, 128, 4, 1);
+            else PU_X6(128, 64, 2, 2);
 #undef PU_X6
-    } else if (mode == LOAD_CHUNK16) {
-        if (bm == 256) hipLaunchKernelGGL((igemm_dma_kernel<256, 64, 4, 1, 3>), grid, dim3(256), 0, s, p);
-        else if (bm == 128 && bn == 128) hipLaunchKernelGGL((igemm_dma_kernel<128, 128, 2, 2, 3>), grid, dim3(256), 0, s, p);
-        else if (bm == 128) hipLaunchKernelGGL((igemm_dma_kernel<128, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((igemm_dma_kernel<64, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
-    } else if (bm == 256) launch_mode<256, 64, 4, 1>(mode, p, grid, s);
-    else if (bm == 128 && bn == 128) launch_mode<128, 128, 2, 2>(mode, p, grid, s);
-    else if (bm == 128) launch_mode<128, 64, 2, 2>(mode, p, grid, s);
-    else launch_mode<64, 64, 2, 2>(mode, p, grid, s);
+            break;
+        case CK_DMA:
+            if (bm == 256) hipLaunchKernelGGL((igemm_dma_kernel<256, 64, 4, 1, 3>), grid, dim3(256), 0, s, p);
+            else if (bm == 128 && bn == 128) hipLaunchKernelGGL((igemm_dma_kernel<128, 128, 2, 2, 3>), grid, dim3(256), 0, s, p);
+            else if (bm == 128) hipLaunchKernelGGL((igemm_dma_kernel<128, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((igemm_dma_kernel<64, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
+            break;
+        default:
+            if (bm == 256) launch_mode<256, 64, 4, 1>(pl.mode, p, grid, s);
+            else if (bm == 128 && bn == 128) launch_mode<128, 128, 2, 2>(pl.mode, p, grid, s);
+            else if (bm == 128) launch_mode<128, 64, 2, 2>(pl.mode, p, grid, s);
+            else launch_mode<64, 64, 2, 2>(pl.mode, p, grid, s);
+    }
     if (p.ksplit > 1) {
         const long long threads = M * (N / 4);
         hipLaunchKernelGGL(igemm_splitk_epilogue_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, p);
     }
-    return check_launch("pu_conv_igemm");
+    return check_launch(what);
 }
 
 extern "C" int pu_split_weight6(const float* packed, void* out, int n, int k_pad, void* stream) {
@@ -1673,60 +1693,15 @@ extern "C" int pu_split_weight6(const float* packed, void* out, int n, int k_pad
 
 extern "C" size_t pu_conv_igemm_workspace_bytes(const pu_conv_args* a) {
     if (!a || a->batch <= 0 || a->out_h <= 0 || a->out_w <= 0 || a->n <= 0 || a->k_pad <= 0) return 0;
-    const long long M = (long long)a->batch * a->out_h * a->out_w;
-    if (small_conv_ok(a) || stem_conv_ok(a) || conv1x1_small_ok(a) || smallx6_ok(a, vec_epilogue(a))) return 0;
-    if (wino_ok(a, vec_epilogue(a))) return wino_workspace_bytes(a);
-    int bm, bn, ks, tp;
-    plan_tiles(a, M, &bm, &bn, &ks, &tp);
-    return split_bytes(M, a->n, ks);
+    return plan_conv(a, (long long)a->batch * a->out_h * a->out_w).ws_bytes;
 }
 
 extern "C" int pu_conv_igemm_tile(const pu_conv_args* a, int* bm, int* bn, int* mode, int* ksplit) {
     PU_REQUIRE(a && bm && bn && mode, "pu_conv_igemm_tile: null args");
-    const long long M = (long long)a->batch * a->out_h * a->out_w;
-    int ks, tp;
-    plan_tiles(a, M, bm, bn, &ks, &tp);
-    *mode = choose_mode(a->c0, a->c1);
-    if (uses_x6(a)) *mode = 4;   // 6-product bf16
-    if (stem_conv_ok(a)) {           // reported as mode 5 ("stem"), tile ST_TH x ST_TW pixels
-        *bm = ST_TH * ST_TW;
-        *bn = a->n;
-        *mode = 5;
-        if (ksplit) *ksplit = 1;
-        return PU_OK;
-    }
-    if (conv1x1_small_ok(a)) {       // reported as mode 3 ("direct"), one pixel per thread
-        *bm = 256;
-        *bn = a->n;
-        *mode = 3;
-        if (ksplit) *ksplit = 1;
-        return PU_OK;
-    }
-    if (smallx6_ok(a, vec_epilogue(a))) {   // reported as mode 7 ("x6s"), 16 x 32 pixels x n (stride 2: 4 x 32)
-        *bm = a->stride == 2 ? 128 : a->kh == 2 ? 256 : 512;
-        *bn = a->n;
-        *mode = 7;
-        if (ksplit) *ksplit = 1;
-        return PU_OK;
-    }
-    if (small_conv_ok(a)) {          // reported as mode 3 ("direct"), tile SC_TH x SC_TW pixels
-        *bm = SC_TH * SC_TW;
-        *bn = a->n;
-        *mode = 3;
-        if (ksplit) *ksplit = 1;
-        return PU_OK;
-    }
-    if (wino_ok(a, vec_epilogue(a))) {  // reported as mode 6 ("wino"): 64 tiles (256 pixels) x 64 channels,
-        const int wc = wino_item_channels(a);      // or 32 tiles (128 pixels) x 128 channels
-        *bm = wc == 64 ? 256 : 128;
-        *bn = wc;
-        *mode = 6;
-        if (ksplit) {
-            const size_t need = wino_workspace_bytes(a);
-            *ksplit = need && a->workspace && a->ws_bytes >= need ? (int)(need / ((size_t)M * a->n * 4)) : 1;
-        }
-        return PU_OK;
-    }
-    if (ksplit) *ksplit = (ks > 1 && a->workspace && a->ws_bytes >= split_bytes(M, a->n, ks)) ? ks : 1;
+    const ConvPlan pl = plan_conv(a, (long long)a->batch * a->out_h * a->out_w);
+    *bm = pl.bm;
+    *bn = pl.bn;
+    *mode = pl.mode;
+    if (ksplit) *ksplit = pl.ksplit;
     return PU_OK;
 }

@@ -12,10 +12,6 @@
 // channels of one pixel, stored as 8 bytes.
 #include "common.h"
 
-#ifndef PU_EPI_BATCH
-#define PU_EPI_BATCH 1   // 0: every output through epi_store4_b (A/B builds)
-#endif
-
 namespace pu {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -122,7 +118,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t epi_rsrc_b(const void* base, b
 }
 
 __device__ __forceinline__ int epi_batch_b_ok(const IgemmBf16Params& p) {
-    if (PU_EPI_BATCH == 0 || (p.flags & (PU_EPI_SHUFFLE2 | PU_EPI_ACCUM)) || p.resid || p.n0 % 32 || p.N % 32 ||
+    if ((p.flags & (PU_EPI_SHUFFLE2 | PU_EPI_ACCUM)) || p.resid || p.n0 % 32 || p.N % 32 ||
         (long long)p.M * p.N >= (1LL << 29))
         return 0;
     const bool mk = p.mask0 || p.mask1;
@@ -201,7 +197,7 @@ __device__ __forceinline__ void epilogue_batched_b(const IgemmBf16Params& p, f32
 // every bias load before the first store (the per-output epi_store4_b waited out each previous
 // store's round trip before its bias load).  Same operations and rounding as epi_store4_b.
 __device__ __forceinline__ bool epi_shuf_b_ok(const IgemmBf16Params& p) {
-    return PU_EPI_BATCH && (p.flags & PU_EPI_SHUFFLE2) && !(p.flags & PU_EPI_ACCUM) && !p.resid && p.bias && !p.mask0 &&
+    return (p.flags & PU_EPI_SHUFFLE2) && !(p.flags & PU_EPI_ACCUM) && !p.resid && p.bias && !p.mask0 &&
            p.shuf_off == 0 && p.shuf_h == 2 * p.Ho && p.shuf_w == 2 * p.Wo && (p.N / 4) % 32 == 0 && p.N % 128 == 0 &&
            (long long)p.M * p.N < (1LL << 29);
 }
@@ -261,60 +257,6 @@ __device__ __forceinline__ void epilogue_batched_shuf_b(const IgemmBf16Params& p
                 for (int e = 0; e < 4; ++e) o[e] = (__bf16)v[e];
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, o), rd, orow[i][j], 16 * q, 0);
             }
-}
-
-// the same epilogue for channels n..n+7 of pixel m (non-SHUFFLE2, n0 % 8 == 0): 16-byte loads and
-// stores, so 8 lanes cover a 64-channel pixel row of 128 contiguous bytes.  bias: preloaded.
-// Every lane issues the same memory operations (a lane whose destination has no mask still loads,
-// from a valid address, and ignores it), so the caller can count them for s_waitcnt: 1 store +
-// one load each for resid / mask / accumulate when the launch uses them (epi8_ops).
-__device__ __forceinline__ int epi8_ops(const IgemmBf16Params& p) {
-    return 1 + (p.resid ? 1 : 0) + ((p.mask0 || p.mask1) ? 1 : 0) + ((p.flags & PU_EPI_ACCUM) ? 1 : 0);
-}
-
-__device__ __forceinline__ void epi_store8_b(const IgemmBf16Params& p, long long m, int n, f32x4 v0, f32x4 v1,
-                                             f32x4 b0, f32x4 b1) {
-    __bf16* dst;
-    const __bf16* msk;
-    long long off;
-    if (n < p.n0) {
-        off = m * p.n0 + n;
-        dst = p.dst0; msk = p.mask0;
-    } else {
-        off = m * (p.N - p.n0) + (n - p.n0);
-        dst = p.dst1; msk = p.mask1;
-    }
-    v0 += b0;
-    v1 += b1;
-    if (p.resid) {
-        const bf16x8 r = *reinterpret_cast<const bf16x8*>(p.resid + off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { v0[e] += (float)r[e]; v1[e] += (float)r[4 + e]; }
-    }
-    if (p.flags & PU_EPI_RELU) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { v0[e] = fmaxf(v0[e], 0.f); v1[e] = fmaxf(v1[e], 0.f); }
-    }
-    if (p.mask0 || p.mask1) {
-        const __bf16* mp = msk ? msk + off : (p.mask0 ? p.mask0 : p.mask1);
-        const bf16x8 mv = *reinterpret_cast<const bf16x8*>(mp);
-        if (msk) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (!((float)mv[e] > 0.f)) v0[e] = 0.f;
-                if (!((float)mv[4 + e] > 0.f)) v1[e] = 0.f;
-            }
-        }
-    }
-    if (p.flags & PU_EPI_ACCUM) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(dst + off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { v0[e] += (float)a[e]; v1[e] += (float)a[4 + e]; }
-    }
-    bf16x8 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = (__bf16)v0[e]; o[4 + e] = (__bf16)v1[e]; }
-    *reinterpret_cast<bf16x8*>(dst + off) = o;
 }
 
 // s_waitcnt vmcnt(base + extra) for a run-time extra in {0, 2, ..., 62 - base} (wave-uniform);
@@ -896,229 +838,6 @@ __global__ __launch_bounds__(HB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
     }
 }
 
-// ---------------------------------------------------------------- halo bf16 kernel, DMA ring
-// The same convolutions as igemm_bf16_halo_kernel (3x3 / s1 / p1, width 32 / 64 / 128), restaged so
-// that nothing waits on HBM: PMC on the register-staged kernel showed MFMA busy 0.21 and waves
-// parked on s_waitcnt / barriers 49 % of their cycles - its next group's halo was loaded one group
-// ahead through registers, then stored to LDS between two barriers.
-//   block: 4 waves (one per SIMD), one block per CU, persistent over an XCD-contiguous tile range;
-//     tile = 512 output pixels (R = 512 / W whole rows of one image) x 64 output channels;
-//     wave = 128 pixels x 64 channels (4 x 2 fragments: 6 fragment reads per 8 MFMAs);
-//   stage = 16 input channels: the (R+2) x (W+2) halo [pixel][16 ch] (32 B per pixel: a 32-pixel
-//     fragment is one contiguous 1 KB run at every tap shift - conflict-free) and the 9 tap slices
-//     of the weights [tap][n][16 k], both written straight into LDS by buffer_load ... lds (32-bit
-//     offsets: per-lane pixel index x the source's pixel stride + a scalar channel offset; padding
-//     and out-of-image pixels get an out-of-range offset and land as zeros);
-//   3-slot ring, loads issued two stages ahead (the next tile's first stages fly over this tile's
-//     last MFMAs and its epilogue), one counted vmcnt + one barrier per stage.
-// K order: group g (32 channels), half h, tap t - a different summation order from the per-tap
-// kernels (fp32 accumulation of exact bf16 products either way).  Host: halo2_ok_b.
-constexpr int H2_NT = 256;
-constexpr int H2_BN = 64;
-#ifndef PU_H2_ABL
-#define PU_H2_ABL 0     // ablation builds only (timing): 1 no halo loads, 2 no weight loads, 3 neither
-#endif
-
-template <int W>
-__global__ __launch_bounds__(H2_NT) void igemm_bf16_halo2_kernel(const IgemmBf16Params p) {
-    constexpr int R = 512 / W;
-    constexpr int HW = W + 2;
-    constexpr int HP = (R + 2) * HW;                  // halo pixels
-    constexpr int HI = (HP * 2 + 63) / 64;            // 1 KB DMA instructions for the halo
-    constexpr int XB = HI * 1024;                     // halo bytes (padded to whole instructions)
-    constexpr int WI = 9 * H2_BN * 2 / 64;            // weight instructions: 18
-    constexpr int STAGE = XB + WI * 1024;
-    constexpr int HPW = (HI + 3) / 4;                 // per wave
-    constexpr int WPW = (WI + 3) / 4;
-    constexpr int LPW = HPW + WPW;                    // loads per wave per stage (dummies included)
-    constexpr int FRAGS = 4;                          // 32-pixel fragments per wave
-    static_assert(R * W == 512 && W % 32 == 0 && 3 * STAGE + 1024 <= 160 * 1024, "halo2 tile");
-
-    extern __shared__ __attribute__((aligned(1024))) char h2_lds[];
-    char* sink = h2_lds + 3 * STAGE;                  // dummy DMA target
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lr = lane & 31, lh = lane >> 5;
-
-    const int ntiles = p.M / 512 * p.gn;
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3;
-    const int tq = (ntiles + 7) >> 3;
-    const int t_end = min(ntiles, (xcd + 1) * tq);
-    const int t_first = xcd * tq + (int)(blockIdx.x >> 3);
-    if (t_first >= t_end) return;                      // uniform per block
-    const int rb = p.Ho / R;
-    const int S = p.C / 16;                            // stages per tile
-    const unsigned wbytes = (unsigned)p.N * (unsigned)p.k_pad * 2u;
-    const unsigned x0bytes = (unsigned)p.in_pix * (unsigned)p.c0 * 2u;
-    const unsigned x1bytes = (unsigned)p.in_pix * (unsigned)p.c1 * 2u;
-
-    // ---- loader state (the stage being issued may belong to the next tile)
-    int ld_tile = t_first, ld_s = 0;
-    int hpix[HPW];                                     // image pixel of this lane's halo piece, -1: zero
-    unsigned hchunk[HPW];
-    unsigned wvo[WPW];                                 // weight byte offset (without the stage's k)
-    auto setup = [&](int t) {
-        const int mt = t / p.gn;
-        const int b = mt / rb;
-        const int r0 = (mt - b * rb) * R;
-#pragma unroll
-        for (int j = 0; j < HPW; ++j) {
-            const int I = wave + 4 * j;
-            const int e = I * 64 + lane;
-            const int hp = e >> 1;
-            const int hr = hp / HW, hc = hp - hr * HW;
-            const int ir = r0 - 1 + hr, ic = hc - 1;
-            const bool ok = I < HI && hp < HP && (unsigned)ir < (unsigned)p.Hi && (unsigned)ic < (unsigned)W;
-            hpix[j] = ok ? (b * p.Hi + ir) * W + ic : -1;
-            hchunk[j] = (unsigned)(e & 1) * 16u;
-        }
-        const int n_blk = (t - mt * p.gn) * H2_BN;
-#pragma unroll
-        for (int j = 0; j < WPW; ++j) {
-            const int I = wave + 4 * j;
-            const int e = I * 64 + lane;
-            const int tap = e >> 7, n = (e >> 1) & 63, ch = e & 1;
-            wvo[j] = I < WI ? (unsigned)((n_blk + n) * p.k_pad + tap * 32 + ch * 8) * 2u : LEAN_OOB;
-        }
-    };
-    auto issue = [&](int slot) {
-        const bool live = ld_tile < t_end;
-        char* base = h2_lds + slot * STAGE;
-        const int g = ld_s >> 1, h = ld_s & 1;
-        const int c = g * 32 + h * 16;
-        const bool second = c >= p.c0;
-        const __bf16* src = second ? p.src1 : p.src0;
-        const unsigned cs2 = (unsigned)(second ? p.c1 : p.c0) * 2u;
-        const unsigned xbytes = live ? (second ? x1bytes : x0bytes) : 0u;
-        const unsigned soff = (unsigned)(second ? c - p.c0 : c) * 2u;
-#pragma unroll
-        for (int j = 0; j < HPW; ++j) {
-            const int I = wave + 4 * j;
-            const unsigned vo = hpix[j] >= 0 ? (unsigned)hpix[j] * cs2 + hchunk[j] : LEAN_OOB;
-            if (PU_H2_ABL != 1 && PU_H2_ABL != 3) lean_load(src, xbytes, I < HI ? base + I * 1024 : sink, vo, soff);
-        }
-        const unsigned wsoff = (unsigned)(g * 288 + h * 16) * 2u;
-#pragma unroll
-        for (int j = 0; j < WPW; ++j) {
-            const int I = wave + 4 * j;
-            if (PU_H2_ABL != 2 && PU_H2_ABL != 3)
-                lean_load(p.wt, live ? wbytes : 0u, I < WI ? base + XB + I * 1024 : sink, wvo[j], wsoff);
-        }
-        if (++ld_s == S) {                             // the next stage opens the next tile
-            ld_s = 0;
-            ld_tile += per_xcd;
-            if (ld_tile < t_end) setup(ld_tile);
-        }
-    };
-
-    // ---- fragment addresses: fragment i = pixels wave*128 + 32 i .. +31 (one image row each)
-    unsigned xa[FRAGS];
-#pragma unroll
-    for (int i = 0; i < FRAGS; ++i) {
-        const int p0 = wave * 128 + 32 * i;
-        const int orow = p0 / W, ocol = p0 - orow * W;
-        xa[i] = (unsigned)((orow * HW + ocol + lr) * 32 + lh * 16);
-    }
-    const unsigned wa = (unsigned)(XB + lr * 32 + lh * 16);
-
-    // memory operations per wave of one tile's epilogue: 4 fragments x 4 pixel passes x epi8_ops,
-    // plus the two bias loads
-    const int EOPS = 16 * epi8_ops(p) + (p.bias ? 2 : 0);
-    setup(t_first);
-    issue(0);
-    issue(1);
-    int tile = t_first;
-    int u = 0;                                         // stage counter (ring position)
-    for (;;) {
-        const int mt = tile / p.gn;
-        const int m_blk = mt * 512;
-        const int n_blk = (tile - mt * p.gn) * H2_BN;
-        f32x16 acc[FRAGS][2];
-#pragma unroll
-        for (int i = 0; i < FRAGS; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        for (int s = 0; s < S; ++s, ++u) {
-            // stage u landed.  In a tile's first two stages the previous tile's epilogue (EOPS
-            // memory operations, issued after stage u+1's loads) is still in flight: count it
-            // instead of draining it, so its stores overlap this tile's MFMAs
-            if (s < 2 && tile != t_first) wait_vm_plus<LPW>(EOPS);
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPW) : "memory");
-            __builtin_amdgcn_s_barrier();              // ... for every wave; slot (u+2)%3 is free
-            asm volatile("" ::: "memory");
-            const int slot = u % 3;
-            issue(slot == 0 ? 2 : slot - 1);
-            const char* a = h2_lds + slot * STAGE;
-            // fragments double-buffered one tap ahead; the scheduling barriers keep tap t+1's six
-            // reads ahead of tap t's eight MFMAs (left alone, the scheduler interleaved each read
-            // with its consumer: one wave per SIMD then waits out every LDS latency)
-            bf16x8 fx[2][FRAGS], fw[2][2];
-            auto frag = [&](int t, int bsel) {
-                const int toff = ((t / 3) * HW + (t % 3)) * 32;
-#pragma unroll
-                for (int i = 0; i < FRAGS; ++i) fx[bsel][i] = *reinterpret_cast<const bf16x8*>(a + xa[i] + toff);
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    fw[bsel][j] = *reinterpret_cast<const bf16x8*>(a + wa + (t * H2_BN + j * 32) * 32);
-            };
-            frag(0, 0);
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                if (t + 1 < 9) frag(t + 1, (t + 1) & 1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < FRAGS; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[t & 1][j], fx[t & 1][i], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // epilogue through the ring slot this stage just consumed (free until the next stage's
-        // issue, which follows a barrier): per 32-pixel fragment, the wave's 32 x 64 fp32 tile
-        // goes to LDS [pixel][68 floats] (conflict-free b128 writes), and comes back as 8
-        // channels of one pixel per lane - every store is a full 128-byte pixel row segment
-        // (the MFMA layout would store 8 bytes per lane and 64 pieces per instruction)
-        __builtin_amdgcn_s_barrier();                  // every wave is done reading the slot
-        asm volatile("" ::: "memory");
-        float* ep = reinterpret_cast<float*>(h2_lds + ((u - 1) % 3) * STAGE) + wave * (32 * 68);
-        const int rp = lane >> 3, c8 = (lane & 7) * 8;  // read-back: pixel rp (+8 per pass), channels c8..
-        f32x4 b0 = f32x4{0.f, 0.f, 0.f, 0.f}, b1 = b0;
-        if (p.bias) {
-            b0 = *reinterpret_cast<const f32x4*>(p.bias + n_blk + c8);
-            b1 = *reinterpret_cast<const f32x4*>(p.bias + n_blk + c8 + 4);
-        }
-#pragma unroll
-        for (int i = 0; i < FRAGS; ++i) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                    *reinterpret_cast<f32x4*>(ep + lr * 68 + j * 32 + 8 * q + 4 * lh) = v;
-                }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // own wave's tile only: no barrier
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) {
-                const int px = ps * 8 + rp;
-                const f32x4 v0 = *reinterpret_cast<const f32x4*>(ep + px * 68 + c8);
-                const f32x4 v1 = *reinterpret_cast<const f32x4*>(ep + px * 68 + c8 + 4);
-                epi_store8_b(p, (long long)(m_blk + wave * 128 + i * 32 + px), n_blk + c8, v0, v1, b0, b1);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads done before the next fragment's writes
-        }
-        tile += per_xcd;
-        if (tile >= t_end) break;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the trailing (dead) loads drain before exit
-}
-
 // ---------------------------------------------------------------- row-stream bf16 kernel
 // The 128-wide, 64 -> 64 channel 3x3 convolutions of config C3's top level (inc.conv2 and
 // up4.conv2, fwd and dgrad: 4 of the 6 top-level launches, ~77 us each on the halo kernel at 0.2 of
@@ -1137,13 +856,6 @@ __global__ __launch_bounds__(H2_NT) void igemm_bf16_halo2_kernel(const IgemmBf16
 //     start of its step (they land under its MFMAs), 8-byte stores.
 // K order (32-channel group, tap, 16-channel half) and the MFMA sequence per accumulator are
 // igemm_bf16_halo_kernel's, so the two are bit-identical.  Host: rows_ok_b.
-#ifndef PU_RS_PD
-#define PU_RS_PD 4      // k-steps of fragment reads in flight (A/B builds: 2, 3, 4)
-#endif
-#ifndef PU_RS_ABL
-#define PU_RS_ABL 0     // ablation builds only (timing): 1 no output stores, 2 no MFMAs, 3 no per-row wait/barrier,
-// 4 in-loop row loads with an empty range (no HBM reads), 5 weights with an empty range
-#endif
 constexpr int RS_W = 128, RS_ROWS = 16, RS_RING = 5;
 constexpr int RS_ROWB = (RS_W + 2) * 128;                        // 16640 B per ring row
 constexpr int RS_WB = 9 * 64 * 128;                              // 73728 B of weights
@@ -1175,7 +887,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_rows_kernel(const IgemmBf16Par
         const int tap = row >> 6, n = row & 63;
         const int c = (lane & 7) ^ ((row >> 1) & 7);
         const unsigned vo = (unsigned)(n * p.k_pad + (c >> 2) * 288 + tap * 32 + (c & 3) * 8) * 2u;
-        lean_load(p.wt, PU_RS_ABL == 5 ? 0u : wbytes, wl + I * 1024, vo, 0u);
+        lean_load(p.wt, wbytes, wl + I * 1024, vo, 0u);
     }
     // input row ir of image b -> ring slot (ir + 1) % RS_RING, pixels 1 .. 128 (4 x 1 KB per wave)
     unsigned xvo[4];
@@ -1192,7 +904,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_rows_kernel(const IgemmBf16Par
         const unsigned soff = ok ? (unsigned)((b * p.Hi + ir) * RS_W) * 128u : 0u;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            lean_load(p.src0, ok && !(PU_RS_ABL == 4 && ir > r0 + 2) ? xbytes : 0u, base + (wave + 4 * j) * 1024, xvo[j], soff);
+            lean_load(p.src0, ok ? xbytes : 0u, base + (wave + 4 * j) * 1024, xvo[j], soff);
     };
     load_row(r0 - 1);
     load_row(r0);
@@ -1243,10 +955,9 @@ __global__ __launch_bounds__(256) void igemm_bf16_rows_kernel(const IgemmBf16Par
         if (r == r0) {
             wait_vm_plus<4>(E);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // + the padding zeros
-        } else if (PU_RS_ABL == 3) asm volatile("" ::: "memory");
-        else if (r == r0 + 1) wait_vm_plus<12>(2 * E);
+        } else if (r == r0 + 1) wait_vm_plus<12>(2 * E);
         else wait_vm_plus<20>(2 * E);
-        if (PU_RS_ABL != 3 || r == r0) __builtin_amdgcn_s_barrier();   // ... for every wave; slot of row r-2 free
+        __builtin_amdgcn_s_barrier();   // ... for every wave; slot of row r-2 free
         asm volatile("" ::: "memory");
         const long long m = (long long)(b * p.Ho + r) * RS_W + q0 + lr;
         load_row(r + 3);
@@ -1260,7 +971,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_rows_kernel(const IgemmBf16Par
         // fragment reads RS_PD k-steps ahead (3 x 16 B per step; 12 in flight at RS_PD = 4 - one wave
         // per SIMD has no partner wave to cover the LDS latency: at 2 steps ahead the loop ran at the
         // read latency, 3.4 us per row with or without its MFMAs)
-        constexpr int RS_PD = PU_RS_PD, NB = RS_PD + 1;
+        constexpr int RS_PD = 4, NB = RS_PD + 1;
         bf16x8 fx[NB], fw[NB][2];
         auto rd = [&](auto S) {
             constexpr int s = decltype(S)::value;
@@ -1276,10 +987,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_rows_kernel(const IgemmBf16Par
             if constexpr (s + RS_PD < 36) rd(std::integral_constant<int, s + RS_PD>{});
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                if (PU_RS_ABL == 2) acc[j][s & 15] += __builtin_bit_cast(float, __builtin_shufflevector(fw[s % NB][j], fx[s % NB], 0, 9));
-                else acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[s % NB][j], fx[s % NB], acc[j], 0, 0, 0);
-            }
+            for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[s % NB][j], fx[s % NB], acc[j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         });
 
@@ -1311,7 +1019,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_rows_kernel(const IgemmBf16Par
                 bf16x4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = (__bf16)v[e];
-                if (PU_RS_ABL != 1 || (p.flags & (1 << 30))) *reinterpret_cast<bf16x4*>(p.dst0 + m * 64 + j * 32 + 8 * q + 4 * lh) = o;
+                *reinterpret_cast<bf16x4*>(p.dst0 + m * 64 + j * 32 + 8 * q + 4 * lh) = o;
             }
         if (E && r + 1 < r0 + RS_ROWS) prefetch(r + 1);
     }
@@ -1329,34 +1037,6 @@ __global__ __launch_bounds__(256) void igemm_bf16_splitk_epilogue_kernel(const I
     f32x4 v = *reinterpret_cast<const f32x4*>(src);
     for (int z = 1; z < p.ksplit; ++z) v += *reinterpret_cast<const f32x4*>(src + z * mn);
     epi_store4_b(p, epi_row_b(p, m), n, v);
-}
-
-static int blocks_for_b(long long M, int N, int bm, int bn) { return ceil_div(M, bm) * ceil_div(N, bn); }
-
-static void choose_tile_b(long long M, int N, int* bm, int* bn) {
-    const int target = 480;
-    if (N <= 64) {
-        if (blocks_for_b(M, N, 256, 64) >= target) { *bm = 256; *bn = 64; }
-        else if (blocks_for_b(M, N, 128, 64) >= target) { *bm = 128; *bn = 64; }
-        else { *bm = 64; *bn = 64; }
-    } else {
-        if (blocks_for_b(M, N, 128, 128) >= target) { *bm = 128; *bn = 128; }
-        else if (blocks_for_b(M, N, 128, 64) >= target) { *bm = 128; *bn = 64; }
-        else { *bm = 64; *bn = 64; }
-    }
-}
-
-static void plan_split_b(const pu_conv_args* a, long long M, int bm, int bn, int* ksplit, int* t_per) {
-    const int T = a->k_pad / BK16;
-    *ksplit = 1;
-    *t_per = T;
-    const int occ = (bm == 256) ? 2 : (bm == 128 && bn == 128) ? 3 : 4;
-    const int blocks = blocks_for_b(M, a->n, bm, bn);
-    int ks = (256 * occ) / blocks;
-    if (ks > T / 4) ks = T / 4;
-    if (ks < 2) return;
-    *t_per = ceil_div(T, ks);
-    *ksplit = ceil_div(T, *t_per);
 }
 
 // the halo kernel: 3x3 / s1 / p1 same-size, width 32 / 64 / 128, whole 256-pixel row blocks,
@@ -1383,36 +1063,13 @@ static int device_cus_b() {
     return cus[dev];
 }
 
-// the DMA-ring halo kernel: the halo kernel's shapes with 512-pixel row blocks (R = 512 / W rows);
-// opt-in with PU_CONV_HALO_DMA (A/B runs, its bit-identity test); the default is the register-staged
-// kernel, which the Python host runs too
-static bool halo2_ok_b(const pu_conv_args* a) {
-    // its epilogue stores 8 channels (16 B) per lane: 8-channel split point, 16-byte-aligned tensors
-    const uintptr_t ae = (uintptr_t)a->dst0 | (uintptr_t)a->dst1 | (uintptr_t)a->mask0 | (uintptr_t)a->mask1 |
-                         (uintptr_t)a->resid;
-    return halo_ok_b(a) && (a->flags & PU_CONV_HALO_DMA) && a->out_h % (512 / a->out_w) == 0 && a->n0 % 8 == 0 &&
-           (ae & 15) == 0;
-}
-
 // the row-stream kernel: the halo kernel's 3x3 / s1 / p1 shapes restricted to width 128, one
-// 64-channel source, 64 output channels into one destination, 16-row strips; PU_BF16_ROWS=0 keeps
-// the halo kernel (A/B runs)
+// 64-channel source, 64 output channels into one destination, 16-row strips
 static bool rows_ok_b(const pu_conv_args* a) {
-    static const bool on = [] {
-        const char* e = getenv("PU_BF16_ROWS");
-        return !(e && e[0] == '0');
-    }();
-    if (!on || !halo_ok_b(a) || (a->flags & PU_CONV_HALO_DMA)) return false;   // the DMA ring when opted in
+    if (!halo_ok_b(a)) return false;
     if (a->out_w != RS_W || a->out_h % RS_ROWS || a->c0 != 64 || a->c1 != 0 || a->n != 64) return false;
     if (a->n0 != 0 && a->n0 != 64) return false;
     return (long long)a->batch * a->in_h * a->in_w * 128 < (1LL << 31);
-}
-
-template <int W>
-static size_t halo2_lds_bytes() {
-    constexpr int HP = (512 / W + 2) * (W + 2);
-    constexpr int STAGE = (HP * 2 + 63) / 64 * 1024 + 18 * 1024;
-    return 3 * STAGE + 1024;
 }
 
 // the lean kernel: 3x3, 32-channel K groups, one pixel stride for both sources, K == k_pad,
@@ -1428,60 +1085,77 @@ static bool lean_ok_b(const pu_conv_args* a) {
     return true;
 }
 
+// What one call runs: the kernel (the kind pu_conv_igemm_bf16_tile reports), its tile, its K split
+// and the scratch the planned split needs.  pu_conv_igemm_bf16 launches the plan, the two queries
+// report it.
+enum { B16_TILE = 0, B16_LEAN = 1, B16_HALO = 2, B16_ROWS = 3 };
+struct Bf16Plan {
+    int kind, bm, bn;
+    int ksplit, t_per;      // the split this call runs: 1 without the scratch the plan asks for
+    size_t ws_bytes;        // fp32 partial tiles of the planned split (0: the plan does not split)
+};
+
 // lean tiles: 256 x 128 (N > 64) or 256 x 64, 4 waves, ~2 resident blocks per CU (72 / 61 KB of
 // LDS); small pixel grids split K on group boundaries until ~2 blocks per CU
-// 128 x 128 tiles instead of a K split when they alone give a round of blocks (C3's 16^2 level:
-// 256 tiles; the split's fp32 partials cost 2 x 67 MB per layer there): l4 fwd / dgrad 65 / 70 ->
-// 56 / 56 us, C3 +0.8 %; PU_BF16_LEAN128=0 keeps the split (A/B runs)
-static bool lean128_on() {
-    static const bool on = [] {
-        const char* e = getenv("PU_BF16_LEAN128");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-static bool smallm_on() {             // PU_BF16_SMALLM=0: the 256 x 128 split (A/B runs)
-    static const bool on = [] {
-        const char* e = getenv("PU_BF16_SMALLM");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-static void plan_lean_b(const pu_conv_args* a, long long M, int* bm, int* bn, int* ksplit, int* t_per) {
-    *bm = 256;
-    *bn = a->n > 64 ? 128 : 64;
+static void plan_lean_b(const pu_conv_args* a, long long M, Bf16Plan* pl) {
     const int T = a->k_pad / BK16;
-    *ksplit = 1;
-    *t_per = T;
-    const int tiles = blocks_for_b(M, a->n, *bm, *bn);
     const int target = 512;
+    pl->bm = 256;
+    pl->bn = a->n > 64 ? 128 : 64;
+    int tiles = blocks_for(M, a->n, pl->bm, pl->bn);
     if (tiles >= target - target / 16) return;
-    const int t128 = blocks_for_b(M, a->n, 128, 128);
-    if (lean128_on() && a->n > 64 && t128 >= 240) {
-        *bm = 128;
-        return;
-    }
-    // small pixel grids (the 8^2 / 16^2 levels): 128 x 128 tiles split to ~2 blocks per CU.  The
-    // 256 x 128 tiles split 8 / 16 ways wrote 8 - 16 fp32 partial tiles per output (67 MB per 8^2
-    // layer, read back by the split epilogue) for blocks that ran 1 - 2 channel groups each
-    // (PU_BF16_LEAN128=0 with t128 >= 240 keeps the old 256 x 128 split: the A/B switch above)
-    if (smallm_on() && a->n > 64 && (lean128_on() || t128 < 240)) {
-        int k2 = ceil_div(target, t128);
-        if (k2 > T / 9) k2 = T / 9;
-        *bm = 128;
-        if (k2 >= 2) {
-            *t_per = ceil_div(ceil_div(T, k2), 9) * 9;
-            *ksplit = ceil_div(T, *t_per);
-        }
-        return;
+    if (a->n > 64) {
+        // 128 x 128 tiles instead of a K split when they alone give a round of blocks (C3's 16^2
+        // level: 256 tiles; the split's fp32 partials cost 2 x 67 MB per layer there): l4 fwd /
+        // dgrad 65 / 70 -> 56 / 56 us, C3 +0.8 %.  Smaller pixel grids (the 8^2 / 16^2 levels) split
+        // the 128 x 128 tiles to ~2 blocks per CU: 256 x 128 tiles split 8 / 16 ways wrote 8 - 16
+        // fp32 partial tiles per output (67 MB per 8^2 layer, read back by the split epilogue) for
+        // blocks that ran 1 - 2 channel groups each
+        pl->bm = 128;
+        tiles = blocks_for(M, a->n, 128, 128);
+        if (tiles >= 240) return;
     }
     int ks = ceil_div(target, tiles);
     if (ks > T / 9) ks = T / 9;
     if (ks < 2) return;
-    *t_per = ceil_div(ceil_div(T, ks), 9) * 9;
-    *ksplit = ceil_div(T, *t_per);
+    pl->t_per = ceil_div(ceil_div(T, ks), 9) * 9;
+    pl->ksplit = ceil_div(T, pl->t_per);
+}
+
+// The dispatch ladder: rows, halo, lean, tiled.  a has passed setup_bf16.
+static Bf16Plan plan_conv_b(const pu_conv_args* a, long long M) {
+    Bf16Plan pl;
+    pl.ksplit = 1;
+    pl.t_per = a->k_pad / BK16;
+    pl.ws_bytes = 0;
+    if (rows_ok_b(a)) {               // one 128-pixel row x 64 channels per step
+        pl.kind = B16_ROWS;
+        pl.bm = RS_W;
+        pl.bn = 64;
+        return pl;
+    }
+    if (halo_ok_b(a)) {               // 256 pixels x 64 channels, no split
+        pl.kind = B16_HALO;
+        pl.bm = 256;
+        pl.bn = HB_BN;
+        return pl;
+    }
+    if (lean_ok_b(a)) {
+        pl.kind = B16_LEAN;
+        plan_lean_b(a, M, &pl);
+    } else {
+        pl.kind = B16_TILE;
+        choose_tile(M, a->n, &pl.bm, &pl.bn);
+        plan_split(a->k_pad, BK16, 4, M, a->n, pl.bm, pl.bn, &pl.ksplit, &pl.t_per);
+    }
+    if (pl.ksplit > 1) {
+        pl.ws_bytes = (size_t)pl.ksplit * (size_t)M * (size_t)a->n * sizeof(float);
+        if (!a->workspace || a->ws_bytes < pl.ws_bytes) {     // no or too little scratch: unsplit
+            pl.ksplit = 1;
+            pl.t_per = a->k_pad / BK16;
+        }
+    }
+    return pl;
 }
 
 static int setup_bf16(const pu_conv_args* a, IgemmBf16Params* pp, long long* Mout) {
@@ -1540,15 +1214,7 @@ extern "C" size_t pu_conv_igemm_bf16_workspace_bytes(const pu_conv_args* a) {
     IgemmBf16Params p;
     long long M;
     if (setup_bf16(a, &p, &M) != PU_OK) return 0;
-    int bm, bn, ks, tp;
-    if (halo_ok_b(a)) return 0;
-    if (lean_ok_b(a)) {
-        plan_lean_b(a, M, &bm, &bn, &ks, &tp);
-    } else {
-        choose_tile_b(M, a->n, &bm, &bn);
-        plan_split_b(a, M, bm, bn, &ks, &tp);
-    }
-    return ks > 1 ? (size_t)ks * (size_t)M * (size_t)a->n * sizeof(float) : 0;
+    return plan_conv_b(a, M).ws_bytes;
 }
 
 extern "C" int pu_conv_igemm_bf16(const pu_conv_args* a, void* stream) {
@@ -1556,64 +1222,45 @@ extern "C" int pu_conv_igemm_bf16(const pu_conv_args* a, void* stream) {
     long long M;
     int st = setup_bf16(a, &p, &M);
     if (st != PU_OK) return st;
+    const Bf16Plan pl = plan_conv_b(a, M);
     const int N = a->n;
     hipStream_t s = as_stream(stream);
-    if (rows_ok_b(a)) {
-        p.ksplit = 1;
-        p.gn = 1;
-        const dim3 rgrid((unsigned)(a->batch * (a->out_h / RS_ROWS)));
-        hipLaunchKernelGGL(igemm_bf16_rows_kernel, rgrid, dim3(256), RS_LDS, s, p);
-        return check_launch("pu_conv_igemm_bf16 (rows)");
-    }
-    if (halo2_ok_b(a)) {
-        p.ksplit = 1;
-        p.gn = N / H2_BN;
-        const long long tiles = M / 512 * p.gn;
-        const long long per_xcd = ceil_div(tiles, 8LL);
-        const int blocks_per_xcd = device_cus_b() / 8;        // one block per CU
-        const dim3 hgrid((unsigned)(8 * (per_xcd < blocks_per_xcd ? per_xcd : blocks_per_xcd)));
-        if (a->out_w == 128)
-            hipLaunchKernelGGL((igemm_bf16_halo2_kernel<128>), hgrid, dim3(H2_NT), halo2_lds_bytes<128>(), s, p);
-        else if (a->out_w == 64)
-            hipLaunchKernelGGL((igemm_bf16_halo2_kernel<64>), hgrid, dim3(H2_NT), halo2_lds_bytes<64>(), s, p);
-        else
-            hipLaunchKernelGGL((igemm_bf16_halo2_kernel<32>), hgrid, dim3(H2_NT), halo2_lds_bytes<32>(), s, p);
-        return check_launch("pu_conv_igemm_bf16 (halo2)");
-    }
-    if (halo_ok_b(a)) {
-        p.ksplit = 1;
-        p.gn = N / HB_BN;
-        const long long tiles = M / 256 * p.gn;
-        const long long per_xcd = ceil_div(tiles, 8LL);
-        const int blocks_per_xcd = 2 * device_cus_b() / 8;   // 2 resident blocks per CU
-        const dim3 hgrid((unsigned)(8 * (per_xcd < blocks_per_xcd ? per_xcd : blocks_per_xcd)));
-        if (a->out_w == 128) hipLaunchKernelGGL((igemm_bf16_halo_kernel<128>), hgrid, dim3(HB_NT), 0, s, p);
-        else if (a->out_w == 64) hipLaunchKernelGGL((igemm_bf16_halo_kernel<64>), hgrid, dim3(HB_NT), 0, s, p);
-        else hipLaunchKernelGGL((igemm_bf16_halo_kernel<32>), hgrid, dim3(HB_NT), 0, s, p);
-        return check_launch("pu_conv_igemm_bf16 (halo)");
-    }
-    int bm, bn;
-    const bool lean = lean_ok_b(a);
-    if (lean) {
-        plan_lean_b(a, M, &bm, &bn, &p.ksplit, &p.t_per);
-    } else {
-        choose_tile_b(M, N, &bm, &bn);
-        plan_split_b(a, M, bm, bn, &p.ksplit, &p.t_per);
-    }
-    p.gn = ceil_div(N, bn);
-    if (p.ksplit > 1 && (!a->workspace || a->ws_bytes < (size_t)p.ksplit * M * N * sizeof(float))) {
-        p.ksplit = 1;
-        p.t_per = a->k_pad / BK16;
-    }
+    p.ksplit = pl.ksplit;
+    p.t_per = pl.t_per;
     p.part = (float*)a->workspace;
-    const dim3 grid(ceil_div(M, bm) * p.gn * p.ksplit);
-    if (lean && bm == 128) hipLaunchKernelGGL((igemm_bf16_lean_kernel<128, 128, 2, 2, 4>), grid, dim3(256), 0, s, p);
-    else if (lean && bn == 128) hipLaunchKernelGGL((igemm_bf16_lean_kernel<256, 128, 2, 2, 4>), grid, dim3(256), 0, s, p);
-    else if (lean) hipLaunchKernelGGL((igemm_bf16_lean_kernel<256, 64, 4, 1, 4>), grid, dim3(256), 0, s, p);
-    else if (bm == 256) hipLaunchKernelGGL((igemm_bf16_kernel<256, 64, 4, 1, 3>), grid, dim3(256), 0, s, p);
-    else if (bm == 128 && bn == 128) hipLaunchKernelGGL((igemm_bf16_kernel<128, 128, 2, 2, 3>), grid, dim3(256), 0, s, p);
-    else if (bm == 128) hipLaunchKernelGGL((igemm_bf16_kernel<128, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((igemm_bf16_kernel<64, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
+    const int bm = pl.bm, bn = pl.bn;
+    const dim3 grid(ceil_div(M, bm) * ceil_div(N, bn) * pl.ksplit);
+    switch (pl.kind) {
+        case B16_ROWS: {
+            p.gn = 1;
+            const dim3 rgrid((unsigned)(a->batch * (a->out_h / RS_ROWS)));
+            hipLaunchKernelGGL(igemm_bf16_rows_kernel, rgrid, dim3(256), RS_LDS, s, p);
+            return check_launch("pu_conv_igemm_bf16 (rows)");
+        }
+        case B16_HALO: {
+            p.gn = N / HB_BN;
+            const long long tiles = M / 256 * p.gn;
+            const long long per_xcd = ceil_div(tiles, 8LL);
+            const int blocks_per_xcd = 2 * device_cus_b() / 8;   // 2 resident blocks per CU
+            const dim3 hgrid((unsigned)(8 * (per_xcd < blocks_per_xcd ? per_xcd : blocks_per_xcd)));
+            if (a->out_w == 128) hipLaunchKernelGGL((igemm_bf16_halo_kernel<128>), hgrid, dim3(HB_NT), 0, s, p);
+            else if (a->out_w == 64) hipLaunchKernelGGL((igemm_bf16_halo_kernel<64>), hgrid, dim3(HB_NT), 0, s, p);
+            else hipLaunchKernelGGL((igemm_bf16_halo_kernel<32>), hgrid, dim3(HB_NT), 0, s, p);
+            return check_launch("pu_conv_igemm_bf16 (halo)");
+        }
+        case B16_LEAN:
+            p.gn = ceil_div(N, bn);
+            if (bm == 128) hipLaunchKernelGGL((igemm_bf16_lean_kernel<128, 128, 2, 2, 4>), grid, dim3(256), 0, s, p);
+            else if (bn == 128) hipLaunchKernelGGL((igemm_bf16_lean_kernel<256, 128, 2, 2, 4>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((igemm_bf16_lean_kernel<256, 64, 4, 1, 4>), grid, dim3(256), 0, s, p);
+            break;
+        default:
+            p.gn = ceil_div(N, bn);
+            if (bm == 256) hipLaunchKernelGGL((igemm_bf16_kernel<256, 64, 4, 1, 3>), grid, dim3(256), 0, s, p);
+            else if (bm == 128 && bn == 128) hipLaunchKernelGGL((igemm_bf16_kernel<128, 128, 2, 2, 3>), grid, dim3(256), 0, s, p);
+            else if (bm == 128) hipLaunchKernelGGL((igemm_bf16_kernel<128, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((igemm_bf16_kernel<64, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
+    }
     if (p.ksplit > 1) {
         const long long threads = M * (N / 4);
         hipLaunchKernelGGL(igemm_bf16_splitk_epilogue_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, p);
@@ -1626,35 +1273,10 @@ extern "C" int pu_conv_igemm_bf16_tile(const pu_conv_args* a, int* bm, int* bn, 
     long long M;
     int st = setup_bf16(a, &p, &M);
     if (st != PU_OK) return st;
-    int ks, tp;
-    if (rows_ok_b(a)) {               // the row-stream kernel: one 128-pixel row x 64 channels per step
-        *bm = 128;
-        *bn = 64;
-        if (ksplit) *ksplit = 1;
-        if (kind) *kind = 3;
-        return PU_OK;
-    }
-    if (halo2_ok_b(a)) {              // the DMA-ring halo kernel: 512 pixels x 64 channels
-        *bm = 512;
-        *bn = H2_BN;
-        if (ksplit) *ksplit = 1;
-        if (kind) *kind = 2;
-        return PU_OK;
-    }
-    if (halo_ok_b(a)) {               // the halo kernel: 256 pixels x 64 channels, no split
-        *bm = 256;
-        *bn = HB_BN;
-        if (ksplit) *ksplit = 1;
-        if (kind) *kind = 2;
-        return PU_OK;
-    }
-    if (kind) *kind = lean_ok_b(a) ? 1 : 0;
-    if (lean_ok_b(a)) {
-        plan_lean_b(a, M, bm, bn, &ks, &tp);
-    } else {
-        choose_tile_b(M, a->n, bm, bn);
-        plan_split_b(a, M, *bm, *bn, &ks, &tp);
-    }
-    if (ksplit) *ksplit = (ks > 1 && a->workspace && a->ws_bytes >= (size_t)ks * M * a->n * sizeof(float)) ? ks : 1;
+    const Bf16Plan pl = plan_conv_b(a, M);
+    *bm = pl.bm;
+    *bn = pl.bn;
+    if (ksplit) *ksplit = pl.ksplit;
+    if (kind) *kind = pl.kind;
     return PU_OK;
 }

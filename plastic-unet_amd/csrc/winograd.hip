@@ -857,7 +857,8 @@ void wino_plan(const pu_conv_args* a, int* ksplit, int* kc_per) {
     *ksplit = ceil_div(chunks, per);
 }
 
-int wino_launch(const pu_conv_args* a, IgemmParams p, hipStream_t s) {
+// p.ksplit: the caller's plan - wino_plan's split, or 1 where the call brought too little scratch
+void wino_launch(const pu_conv_args* a, IgemmParams p, hipStream_t s) {
     WinoParams w;
     w.p = p;
     w.U = reinterpret_cast<const __bf16*>(a->wino);
@@ -871,11 +872,10 @@ int wino_launch(const pu_conv_args* a, IgemmParams p, hipStream_t s) {
     w.u_bytes = (unsigned)((long long)(a->c0 + a->c1) * a->n * 96);
     int ks, per;
     wino_plan(a, &ks, &per);
-    if (ks > 1 && (!a->workspace || a->ws_bytes < (size_t)ks * p.M * p.N * sizeof(float))) {
+    if (p.ksplit == 1) {
         ks = 1;
         per = (a->c0 + a->c1) / 16;
     }
-    w.p.ksplit = ks;
     w.p.part = (float*)a->workspace;
     w.kc_per = per;
     const int items = w.gm * w.p.gn * ks;
@@ -889,7 +889,6 @@ int wino_launch(const pu_conv_args* a, IgemmParams p, hipStream_t s) {
         if (full) hipLaunchKernelGGL((wino4_x6_kernel<true, 2>), g, dim3(256), 0, s, w);
         else hipLaunchKernelGGL((wino4_x6_kernel<false, 2>), g, dim3(256), 0, s, w);
     }
-    return ks;
 }
 
 int wino_item_channels(const pu_conv_args* a) { return wino_wide_items(a) ? WG_WIDE_BN : WG_BN; }

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import (ConvArgs, WgradArgs, PlasticArgs, PlasticHeadArgs, PlasticBwdArgs, AdamTensor, PackJob, WinoJob, check,
-                   PU_EPI_RELU, PU_EPI_ACCUM, PU_EPI_SHUFFLE2, PU_EPI_RESID, PU_CONV_NO_HALO, PU_CONV_HALO_V1, PU_CONV_HALO_DMA,
+                   PU_EPI_RELU, PU_EPI_ACCUM, PU_EPI_SHUFFLE2, PU_EPI_RESID, PU_CONV_NO_HALO, PU_CONV_HALO_V1,
                    PU_CONV_NO_SMALLX6, PU_EPI_OUT_BF16)
 
 __all__ = ["KernelProfiler", "igemm", "wgrad", "pack_weight", "nchw_to_nhwc", "maxpool2_fwd", "maxpool2_bwd",
@@ -32,25 +32,24 @@ _MODES = {0: "chunk16", 1: "vec4", 2: "scalar", 3: "direct", 4: "x6", 5: "stem",
 _FP32_MATH = os.environ.get("PU_FP32_MATH", "split6")
 
 
-# bf16 3x3/s1 convolutions of width 32/64/128: 2 = the DMA-ring halo kernel (512-pixel
-# row blocks, PU_CONV_HALO_DMA), 1 = the register-staged halo kernel (default, as at the C-ABI),
-# 0 = the per-tap lean kernel (PU_CONV_HALO:
-# A/B runs; tests flip it with set_conv_halo)
-_CONV_HALO = int(os.environ.get("PU_CONV_HALO", "1"))
+# bf16 3x3/s1 convolutions of width 32/64/128: on = the halo and row-stream kernels (default, as
+# at the C-ABI), off = the per-tap lean kernel (PU_CONV_HALO=0: A/B runs; tests flip it with
+# set_conv_halo)
+_CONV_HALO = os.environ.get("PU_CONV_HALO", "1") != "0"
 
 
-def set_conv_halo(mode):
-    """Route eligible bf16 convolutions: 2 DMA-ring halo kernel, 1 (or True) register-staged halo
-    kernel - the default, as at the C-ABI -, 0 (or False) per-tap kernel.  Returns the previous
-    setting."""
+def set_conv_halo(on):
+    """Route eligible bf16 convolutions: 1 (or True) halo and row-stream kernels - the default, as
+    at the C-ABI -, 0 (or False) per-tap kernel.  Returns the previous setting (1 or 0)."""
     global _CONV_HALO
-    prev, _CONV_HALO = _CONV_HALO, (1 if mode is True else 0 if mode is False else int(mode))
+    if isinstance(on, str) or on not in (0, 1):
+        raise ValueError("set_conv_halo: 1 / True (halo and rows) or 0 / False (per-tap), not %r" % (on,))
+    prev, _CONV_HALO = int(_CONV_HALO), bool(on)
     return prev
 
 
 def _halo_flags():
-    # the C-ABI default (no flag) is the register-staged kernel; 2 opts in to the DMA ring
-    return {2: PU_CONV_HALO_DMA, 1: 0}.get(_CONV_HALO, PU_CONV_NO_HALO)
+    return 0 if _CONV_HALO else PU_CONV_NO_HALO
 
 
 def fp32_math():

@@ -31,9 +31,6 @@ def tag_of(name, grid=None):
     m = re.search(r"igemm_bf16_halo_kernel<(\d+)>", name)
     if m:
         return "igemm_bf16<256x64,halo>"
-    m = re.search(r"igemm_bf16_halo2_kernel<(\d+)>", name)
-    if m:
-        return "igemm_bf16<512x64,halo>"
     m = re.search(r"igemm_bf16_lean_kernel<(\d+), (\d+),", name)
     if m:
         return "igemm_bf16<%sx%s,lean>" % m.groups()

@@ -21,6 +21,8 @@
  *                                                      src/unet/unet_p.py:67-88
  *   pu_trace_update    the trace update alone          src/unet/unet_p.py:81-86
  *   pu_plastic_bwd     mm/mul/sigmoid backward         (autograd, train.py:110)
+ *   pu_plastic_bwd_trace  the same with dL/dhebb' flowing back: dx, dw, dalpha, dhebb, deta
+ *                                                      (autograd of unet_p.py:69-88, hebb kept live)
  *   pu_bce_fwd/bwd     nn.BCELoss (mean, log >= -100)  src/train.py:70,101-105
  *   pu_adam_multi      torch.optim.Adam.step           src/train.py:66,111
  *   pu_bn_fwd/bwd      nn.BatchNorm2d (+ReLU)          src/unet/unet_p.py:186-193 (batch_norm=True)
@@ -420,6 +422,39 @@ typedef struct {
 size_t pu_plastic_bwd_workspace_bytes(int batch, int nbf);
 int pu_plastic_bwd(const pu_plastic_bwd_args* a, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* The same backward with a gradient path through the trace (episodes, learnable eta).  On top of
+ * pu_plastic_bwd it takes dhebb_out = dL/dH' [B][N][N] (NULL: no gradient reached H') and, per slot
+ * with x0 = X_b[0,:], y0 = Y_b[0,:], P = dhebb_out_b:
+ *   hebb: dx0 = eta P y0 ; dy0 = eta P^T x0 ; deta = sum P (.) (x0 y0^T - H)
+ *   oja : dx0 = eta P y0 ; dy0[j] = eta sum_k P[k][j] (x0[k] - 2 H[k][j] y0[j]) ;
+ *         deta = sum P[k][j] y0[j] (x0[k] - H[k][j] y0[j])
+ * dy0 is added to row 0 of dy (dy may be NULL = zeros when dhebb_out is given) before G is formed,
+ * dx0 to row 0 of dx; dw / dalpha as pu_plastic_bwd (same slot order).  dhebb (optional) receives
+ *   dL/dH_b = dH_t + alpha (.) (X_b^T G_b),  dH_t = (1-eta) P (hebb) | P (.) (1 - eta y0[j]^2) (oja)
+ * and deta [1] (required with dhebb_out) the gradient of eta, slots and elements summed in a
+ * fixed order in fp64.  Deterministic (no atomics).  Without dhebb_out: dx, dw, dalpha are bitwise
+ * pu_plastic_bwd's and deta is not written.  The workspace is always required, 16-byte aligned. */
+typedef struct {
+    int batch, nbf, rule;
+    const float* x;
+    const float* hebb;
+    const float* w;
+    const float* alpha;
+    const float* eta;
+    const float* y;
+    const float* dy;
+    const float* dhebb_out;
+    float* dx;
+    float* dw;
+    float* dalpha;
+    float* dhebb;
+    float* deta;
+} pu_plastic_bwd_trace_args;
+
+size_t pu_plastic_bwd_trace_workspace_bytes(int batch, int nbf);
+int pu_plastic_bwd_trace(const pu_plastic_bwd_trace_args* a, void* workspace, size_t workspace_bytes,
+                         void* stream);
 
 /* BCELoss (mean): loss = mean((t-1)*max(log1p(-y),-100) - t*max(log(y),-100))
  * bwd: dy = g * (y-t) / max((1-y)*y, 1e-12) / n, g = *grad_loss (device scalar) */

@@ -608,10 +608,13 @@ __device__ __forceinline__ float sig_bwd(float dy, float y) {
 }
 
 // dX[b][i][k] = sum_j G[b][i][j] * Weff_b[k][j]      grid (N/T, N/T, B)
-template <int T>
+// EX (the trace backward's extras, pu_plastic_bwd_trace): dY may be null (zeros), dy0 [B][N] is
+// added to row 0 of dY before the sigmoid backward and dx0 [B][N] to row 0 of dX.
+template <int T, bool EX = false>
 __global__ __launch_bounds__(256) void head_dx_kernel(const float* __restrict__ Yv, const float* __restrict__ dY,
                                                       const float* __restrict__ H, const float* __restrict__ w,
-                                                      const float* __restrict__ alpha, float* __restrict__ dX, int N) {
+                                                      const float* __restrict__ alpha, float* __restrict__ dX, int N,
+                                                      const float* __restrict__ dy0, const float* __restrict__ dx0) {
 #pragma clang fp contract(off)
     constexpr int M = HeadTile<T>::M;
     __shared__ float gs[HK][T + 4];   // gs[j][i]
@@ -635,7 +638,12 @@ __global__ __launch_bounds__(256) void head_dx_kernel(const float* __restrict__ 
             rdy[u] = ryv[u] = rw[u] = ra[u] = rh[u] = 0.f;
             if (gi < N && gj < N) {
                 const long long o = off + (long long)gi * N + gj;
-                rdy[u] = dY[o];
+                if constexpr (EX) {
+                    rdy[u] = dY ? dY[o] : 0.f;
+                    if (gi == 0) rdy[u] += dy0[(long long)b * N + gj];
+                } else {
+                    rdy[u] = dY[o];
+                }
                 ryv[u] = Yv[o];
             }
             if (gk < N && gj < N) {
@@ -676,17 +684,25 @@ __global__ __launch_bounds__(256) void head_dx_kernel(const float* __restrict__ 
 #pragma unroll
         for (int r = 0; r < M; ++r) {
             int gk = k0 + tx * M + r;
-            if (gk < N) dX[off + (long long)gi * N + gk] = acc[q][r];
+            if (gk < N) {
+                float v = acc[q][r];
+                if constexpr (EX) {
+                    if (gi == 0) v += dx0[(long long)b * N + gk];
+                }
+                dX[off + (long long)gi * N + gk] = v;
+            }
         }
     }
 }
 
 // T_b[k][j] = sum_i X[b][i][k] * G[b][i][j];  per slot: partial[b] = (T_b, T_b * H_b).
 // grid (N/T, N/T, B); the slot sum is a separate fixed-order pass (deterministic)
-template <int T>
+// EX: as head_dx_kernel (dY may be null, dy0 added to its row 0)
+template <int T, bool EX = false>
 __global__ __launch_bounds__(256) void head_dw_kernel(const float* __restrict__ X, const float* __restrict__ Yv,
                                                       const float* __restrict__ dY, const float* __restrict__ H,
-                                                      float* __restrict__ partial, int N) {
+                                                      float* __restrict__ partial, int N,
+                                                      const float* __restrict__ dy0) {
 #pragma clang fp contract(off)
     constexpr int M = HeadTile<T>::M;
     __shared__ float xs[HK][T + 4];   // xs[i][k]
@@ -710,7 +726,12 @@ __global__ __launch_bounds__(256) void head_dw_kernel(const float* __restrict__ 
             rdy[u] = ryv[u] = 0.f;
             if (gi < N && gj < N) {
                 const long long o = off + (long long)gi * N + gj;
-                rdy[u] = dY[o];
+                if constexpr (EX) {
+                    rdy[u] = dY ? dY[o] : 0.f;
+                    if (gi == 0) rdy[u] += dy0[(long long)b * N + gj];
+                } else {
+                    rdy[u] = dY[o];
+                }
                 ryv[u] = Yv[o];
             }
         }
@@ -770,6 +791,179 @@ __global__ void head_dw_reduce_kernel(const float* __restrict__ partial, int B, 
     }
     dw[idx] = sw;
     da[idx] = sa;
+}
+
+// ------------------------------------------------------------------- backward of the trace rule
+// Given P = dL/dH' (pu_plastic_bwd_trace), per slot b with x0 = X_b[0,:], y0 = Y_b[0,:]:
+//   hebb  H' = (1-eta) H + eta x0[k] y0[j]            oja  H' = H + eta (x0[k] - H y0[j]) y0[j]
+//   dx0[k] = eta sum_j P y0[j]                         (both rules)
+//   dy0[j] = eta sum_k P x0[k]                         oja: eta sum_k P (x0[k] - 2 H y0[j])
+//   deta   = sum_bkj P (x0[k] y0[j] - H)               oja: sum_bkj P y0[j] (x0[k] - H y0[j])
+// One read of P and H (8 B N^2 bytes).  A block is 8 groups of 32 lanes; a group walks rows
+// k0 + g, k0 + g + 8 of a TB_ROWS-row chunk, a lane owns V adjacent columns of a 32 V column
+// strip (V = 4: float4 loads).  Row sums: xor tree over the group's lanes -> rowp[b][k][strip];
+// column sums: lane registers over the group's rows, then the 8 groups in order through LDS ->
+// colp[b][chunk][j]; deta: fp64 per lane, LDS tree -> etap[block].  trace_bwd_finish_kernel sums
+// the partials in index order (no atomics anywhere: deterministic).
+constexpr int TB_ROWS = 16;
+
+template <int V>
+__global__ __launch_bounds__(256) void trace_bwd_partial_kernel(const float* __restrict__ P, const float* __restrict__ H,
+                                                                const float* __restrict__ X, const float* __restrict__ Y,
+                                                                int N, int rule, float* __restrict__ rowp,
+                                                                float* __restrict__ colp, double* __restrict__ etap) {
+#pragma clang fp contract(off)
+    __shared__ float cs[8][32 * V];
+    __shared__ double red[256];
+    const int strip = blockIdx.x, chunk = blockIdx.y, b = blockIdx.z;
+    const int nstrips = gridDim.x, nchunks = gridDim.y;
+    const int g = threadIdx.x >> 5, l = threadIdx.x & 31;
+    const long long off = (long long)b * N * N;
+    const int j = strip * 32 * V + l * V;
+    const bool jin = j < N;                       // V = 4 runs only with N % 4 == 0: j < N covers j + 3
+    float y0[V], col[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        y0[e] = jin ? Y[off + j + e] : 0.f;
+        col[e] = 0.f;
+    }
+    double es = 0.0;
+    for (int it = 0; it < TB_ROWS / 8; ++it) {
+        const int k = chunk * TB_ROWS + it * 8 + g;
+        const bool in = jin && k < N;
+        float p[V], h[V];
+        if constexpr (V == 4) {
+            f32x4 pv = {0.f, 0.f, 0.f, 0.f}, hv = pv;
+            if (in) {
+                pv = *reinterpret_cast<const f32x4*>(P + off + (long long)k * N + j);
+                hv = *reinterpret_cast<const f32x4*>(H + off + (long long)k * N + j);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { p[e] = pv[e]; h[e] = hv[e]; }
+        } else {
+            p[0] = in ? P[off + (long long)k * N + j] : 0.f;
+            h[0] = in ? H[off + (long long)k * N + j] : 0.f;
+        }
+        const float x0 = k < N ? X[off + k] : 0.f;
+        float rs = 0.f;
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            rs += p[e] * y0[e];
+            if (rule == PU_RULE_HEBB) {
+                col[e] += p[e] * x0;
+                es += (double)(p[e] * (x0 * y0[e] - h[e]));
+            } else {
+                const float hy = h[e] * y0[e];
+                col[e] += p[e] * (x0 - 2.f * hy);
+                es += (double)(p[e] * y0[e] * (x0 - hy));
+            }
+        }
+        // every lane of the wave takes part (out-of-range lanes carry zeros); the xor distances
+        // stay inside the 32-lane group
+#pragma unroll
+        for (int d = 16; d > 0; d >>= 1) rs += __shfl_xor(rs, d);
+        if (l == 0 && k < N) rowp[((long long)b * N + k) * nstrips + strip] = rs;
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) cs[g][l * V + e] = col[e];
+    red[threadIdx.x] = es;
+    __syncthreads();
+    if (threadIdx.x < 32 * V) {
+        const int jc = strip * 32 * V + threadIdx.x;
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) s += cs[q][threadIdx.x];
+        if (jc < N) colp[((long long)b * nchunks + chunk) * N + jc] = s;
+    }
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) etap[((long long)b * nchunks + chunk) * nstrips + strip] = red[0];
+}
+
+// dx0[b][k] = eta sum_strip rowp, dy0[b][j] = eta sum_chunk colp (grid-stride over B N); block 0
+// also sums the np fp64 deta partials in index order -> deta[0]
+__global__ __launch_bounds__(256) void trace_bwd_finish_kernel(const float* __restrict__ rowp, const float* __restrict__ colp,
+                                                               const double* __restrict__ etap, const float* __restrict__ eta_p,
+                                                               int B, int N, int nstrips, int nchunks, int np,
+                                                               float* __restrict__ dx0, float* __restrict__ dy0,
+                                                               float* __restrict__ deta) {
+#pragma clang fp contract(off)
+    __shared__ double red[256];
+    const float eta = eta_p[0];
+    const long long total = (long long)B * N;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / N), c = (int)(i - (long long)b * N);
+        float sr = 0.f, sc = 0.f;
+        for (int s = 0; s < nstrips; ++s) sr += rowp[i * nstrips + s];
+        for (int q = 0; q < nchunks; ++q) sc += colp[((long long)b * nchunks + q) * N + c];
+        dx0[i] = eta * sr;
+        dy0[i] = eta * sc;
+    }
+    if (blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < np; i += blockDim.x) s += etap[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) deta[0] = (float)red[0];
+}
+
+// dH_b = dH_t + alpha (.) T_b, T_b = the per-slot product head_dw_kernel left in the workspace;
+// dH_t = (1-eta) P (hebb) or P (1 - eta y0[j]^2) (oja), 0 without P.  One pass: 12 B in, 4 B out
+// per element.  grid (ceil(N N / V / 256), B)
+template <int V>
+__global__ __launch_bounds__(256) void head_dh_kernel(const float* __restrict__ P, const float* __restrict__ Y,
+                                                      const float* __restrict__ alpha, const float* __restrict__ partial,
+                                                      const float* __restrict__ eta_p, int N, int rule,
+                                                      float* __restrict__ dH) {
+#pragma clang fp contract(off)
+    const long long nn = (long long)N * N;
+    const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (idx >= nn) return;
+    const int b = blockIdx.y;
+    const long long off = (long long)b * nn;
+    const float* Tb = partial + (long long)b * 2 * nn;
+    const int j = (int)(idx % N);
+    float p[V], t[V], a[V], o[V];
+    if constexpr (V == 4) {
+        const f32x4 tv = *reinterpret_cast<const f32x4*>(Tb + idx), av = *reinterpret_cast<const f32x4*>(alpha + idx);
+        f32x4 pv = {0.f, 0.f, 0.f, 0.f};
+        if (P) pv = *reinterpret_cast<const f32x4*>(P + off + idx);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { p[e] = pv[e]; t[e] = tv[e]; a[e] = av[e]; }
+    } else {
+        p[0] = P ? P[off + idx] : 0.f;
+        t[0] = Tb[idx];
+        a[0] = alpha[idx];
+    }
+    if (P) {
+        const float eta = eta_p[0];
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            float f = 1.f - eta;
+            if (rule != PU_RULE_HEBB) {
+                const float y0 = Y[off + j + e];
+                f = 1.f - eta * (y0 * y0);
+            }
+            o[e] = p[e] * f + a[e] * t[e];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < V; ++e) o[e] = a[e] * t[e];
+    }
+    if constexpr (V == 4) {
+        f32x4 ov;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ov[e] = o[e];
+        *reinterpret_cast<f32x4*>(dH + off + idx) = ov;
+    } else {
+        dH[off + idx] = o[0];
+    }
 }
 
 // --------------------------------------------------------------------------------------------- BCE
@@ -844,8 +1038,12 @@ template <int T>
 static void launch_head_bwd(const pu_plastic_bwd_args* a, float* ws, hipStream_t s) {
     const int N = a->nbf, B = a->batch;
     dim3 grid(ceil_div(N, T), ceil_div(N, T), B);
-    if (a->dx) hipLaunchKernelGGL(head_dx_kernel<T>, grid, dim3(256), 0, s, a->y, a->dy, a->hebb, a->w, a->alpha, a->dx, N);
-    if (ws) hipLaunchKernelGGL(head_dw_kernel<T>, grid, dim3(256), 0, s, a->x, a->y, a->dy, a->hebb, ws, N);
+    if (a->dx)
+        hipLaunchKernelGGL((head_dx_kernel<T, false>), grid, dim3(256), 0, s, a->y, a->dy, a->hebb, a->w, a->alpha, a->dx, N,
+                           (const float*)nullptr, (const float*)nullptr);
+    if (ws)
+        hipLaunchKernelGGL((head_dw_kernel<T, false>), grid, dim3(256), 0, s, a->x, a->y, a->dy, a->hebb, ws, N,
+                           (const float*)nullptr);
 }
 
 }  // namespace pu
@@ -983,6 +1181,113 @@ extern "C" int pu_plastic_bwd(const pu_plastic_bwd_args* a, void* workspace, siz
     hipLaunchKernelGGL(head_dw_reduce_kernel, dim3(ceil_div((long long)N * N, 256)), dim3(256), 0, s,
                        (const float*)ws, B, N, a->dw, a->dalpha);
     return check_launch("pu_plastic_bwd (dw)");
+}
+
+namespace pu {
+
+// workspace of pu_plastic_bwd_trace: [per-slot (T_b, T_b * H_b)] [deta partials, fp64]
+// [dx0] [dy0] [row partials] [column partials]; sized for the scalar path's narrower strips
+struct TraceBwdWs {
+    size_t head, etap, dx0, dy0, rowp, colp, total;   // byte offsets
+};
+
+static TraceBwdWs trace_bwd_ws(int B, int N) {
+    const size_t nchunks = ceil_div(N, TB_ROWS), nstrips = ceil_div(N, 32);
+    TraceBwdWs o;
+    o.head = 0;
+    o.etap = (size_t)B * 2 * N * N * sizeof(float);
+    o.dx0 = o.etap + (size_t)B * nchunks * nstrips * sizeof(double);
+    o.dy0 = o.dx0 + (size_t)B * N * sizeof(float);
+    o.rowp = o.dy0 + (size_t)B * N * sizeof(float);
+    o.colp = o.rowp + (size_t)B * N * nstrips * sizeof(float);
+    o.total = o.colp + (size_t)B * nchunks * N * sizeof(float);
+    return o;
+}
+
+template <int T>
+static void launch_head_bwd_trace(const pu_plastic_bwd_trace_args* a, float* ws, const float* dx0, const float* dy0,
+                                  hipStream_t s) {
+    const int N = a->nbf, B = a->batch;
+    dim3 grid(ceil_div(N, T), ceil_div(N, T), B);
+    if (a->dx)
+        hipLaunchKernelGGL((head_dx_kernel<T, true>), grid, dim3(256), 0, s, a->y, a->dy, a->hebb, a->w, a->alpha, a->dx, N,
+                           dy0, dx0);
+    if (ws) hipLaunchKernelGGL((head_dw_kernel<T, true>), grid, dim3(256), 0, s, a->x, a->y, a->dy, a->hebb, ws, N, dy0);
+}
+
+}  // namespace pu
+
+extern "C" size_t pu_plastic_bwd_trace_workspace_bytes(int batch, int nbf) {
+    if (batch <= 0 || nbf <= 0) return 0;
+    return trace_bwd_ws(batch, nbf).total;
+}
+
+// trace backward -> head backward (with the row-0 extras) -> slot reduction -> dH finish, one stream.
+// Without dhebb_out (no gradient reached H') the head kernels are pu_plastic_bwd's own
+// instantiations: dx, dw, dalpha are bitwise that entry's.
+extern "C" int pu_plastic_bwd_trace(const pu_plastic_bwd_trace_args* a, void* workspace, size_t ws_bytes, void* stream) {
+    PU_REQUIRE(a && a->x && a->hebb && a->w && a->alpha && a->y && a->batch > 0 && a->nbf > 0,
+               "pu_plastic_bwd_trace: bad args");
+    PU_REQUIRE(a->dy || a->dhebb_out, "pu_plastic_bwd_trace: neither dy nor dhebb_out");
+    PU_REQUIRE(a->rule == PU_RULE_HEBB || a->rule == PU_RULE_OJA, "Must select one learning rule ('hebb' or 'oja')");
+    PU_REQUIRE(!a->dhebb_out || (a->eta && a->deta), "pu_plastic_bwd_trace: dhebb_out needs eta and deta");
+    PU_REQUIRE((long long)a->nbf * a->nbf < (1ll << 31), "pu_plastic_bwd_trace: nbf too large");
+    PU_REQUIRE(a->batch <= 65535, "pu_plastic_bwd_trace: batch too large");
+    PU_REQUIRE(!a->dw == !a->dalpha, "pu_plastic_bwd_trace: dw and dalpha go together");
+    const int N = a->nbf, B = a->batch;
+    const TraceBwdWs L = trace_bwd_ws(B, N);
+    if (!workspace || ws_bytes < L.total)
+        return fail(PU_ERR_WORKSPACE, "pu_plastic_bwd_trace: workspace %zu < %zu", ws_bytes, L.total);
+    PU_REQUIRE(((uintptr_t)workspace & 15) == 0, "pu_plastic_bwd_trace: workspace must be 16-byte aligned");
+    hipStream_t s = as_stream(stream);
+    char* base = (char*)workspace;
+    float* wsh = (a->dw || a->dhebb) ? (float*)(base + L.head) : nullptr;
+    const bool vec = N % 4 == 0;
+    if (a->dhebb_out) {
+        double* etap = (double*)(base + L.etap);
+        float* dx0 = (float*)(base + L.dx0);
+        float* dy0 = (float*)(base + L.dy0);
+        float* rowp = (float*)(base + L.rowp);
+        float* colp = (float*)(base + L.colp);
+        const int nchunks = ceil_div(N, TB_ROWS);
+        int nstrips;
+        if (vec && ((((uintptr_t)a->dhebb_out) | ((uintptr_t)a->hebb)) & 15) == 0) {
+            nstrips = ceil_div(N, 128);
+            hipLaunchKernelGGL(trace_bwd_partial_kernel<4>, dim3(nstrips, nchunks, B), dim3(256), 0, s, a->dhebb_out, a->hebb,
+                               a->x, a->y, N, a->rule, rowp, colp, etap);
+        } else {
+            nstrips = ceil_div(N, 32);
+            hipLaunchKernelGGL(trace_bwd_partial_kernel<1>, dim3(nstrips, nchunks, B), dim3(256), 0, s, a->dhebb_out, a->hebb,
+                               a->x, a->y, N, a->rule, rowp, colp, etap);
+        }
+        hipLaunchKernelGGL(trace_bwd_finish_kernel, dim3(grid_for((long long)B * N, 256, 1024)), dim3(256), 0, s,
+                           (const float*)rowp, (const float*)colp, (const double*)etap, a->eta, B, N, nstrips, nchunks,
+                           B * nchunks * nstrips, dx0, dy0, a->deta);
+        int st = check_launch("pu_plastic_bwd_trace (trace)");
+        if (st != PU_OK) return st;
+        if (head_small_tiles(B, N)) launch_head_bwd_trace<32>(a, wsh, dx0, dy0, s);
+        else launch_head_bwd_trace<64>(a, wsh, dx0, dy0, s);
+    } else {
+        pu_plastic_bwd_args h = {B, N, a->x, a->hebb, a->w, a->alpha, a->y, a->dy, a->dx, nullptr, nullptr};
+        if (head_small_tiles(B, N)) launch_head_bwd<32>(&h, wsh, s);
+        else launch_head_bwd<64>(&h, wsh, s);
+    }
+    int st = check_launch("pu_plastic_bwd_trace (head)");
+    if (st != PU_OK || !wsh) return st;
+    if (a->dw) {
+        hipLaunchKernelGGL(head_dw_reduce_kernel, dim3(ceil_div((long long)N * N, 256)), dim3(256), 0, s,
+                           (const float*)wsh, B, N, a->dw, a->dalpha);
+    }
+    if (a->dhebb) {
+        const float* P = a->dhebb_out;
+        if (vec && ((((uintptr_t)P) | ((uintptr_t)a->dhebb) | ((uintptr_t)a->alpha)) & 15) == 0)
+            hipLaunchKernelGGL(head_dh_kernel<4>, dim3(ceil_div((long long)N * N / 4, 256), B), dim3(256), 0, s, P, a->y,
+                               a->alpha, (const float*)wsh, a->eta, N, a->rule, a->dhebb);
+        else
+            hipLaunchKernelGGL(head_dh_kernel<1>, dim3(ceil_div((long long)N * N, 256), B), dim3(256), 0, s, P, a->y,
+                               a->alpha, (const float*)wsh, a->eta, N, a->rule, a->dhebb);
+    }
+    return check_launch("pu_plastic_bwd_trace (dw, dH)");
 }
 
 extern "C" size_t pu_bce_workspace_bytes(long long n) {

@@ -61,6 +61,12 @@ class PlasticBwdArgs(ctypes.Structure):
                 ("dy", P), ("dx", P), ("dw", P), ("dalpha", P)]
 
 
+class PlasticBwdTraceArgs(ctypes.Structure):
+    _fields_ = [("batch", c_int), ("nbf", c_int), ("rule", c_int), ("x", P), ("hebb", P), ("w", P), ("alpha", P),
+                ("eta", P), ("y", P), ("dy", P), ("dhebb_out", P), ("dx", P), ("dw", P), ("dalpha", P), ("dhebb", P),
+                ("deta", P)]
+
+
 class AdamTensor(ctypes.Structure):
     _fields_ = [("param", P), ("grad", P), ("exp_avg", P), ("exp_avg_sq", P), ("numel", c_ll)]
 
@@ -126,6 +132,8 @@ SIGNATURES = [
     ("pu_trace_update", c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
     ("pu_plastic_bwd_workspace_bytes", c_size, [c_int, c_int]),
     ("pu_plastic_bwd", c_int, [ctypes.POINTER(PlasticBwdArgs), P, c_size, P]),
+    ("pu_plastic_bwd_trace_workspace_bytes", c_size, [c_int, c_int]),
+    ("pu_plastic_bwd_trace", c_int, [ctypes.POINTER(PlasticBwdTraceArgs), P, c_size, P]),
     ("pu_bce_workspace_bytes", c_size, [c_ll]),
     ("pu_bce_fwd", c_int, [P, P, c_ll, P, P, c_size, P]),
     ("pu_bce_bwd", c_int, [P, P, c_ll, P, P, P]),

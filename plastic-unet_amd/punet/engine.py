@@ -152,6 +152,45 @@ class Trainer:
         self.sched.step()
         return self._gloss.clone(), self._ghn
 
+    def step_episode(self, xs, ts, hebb):
+        """One optimisation step over an episode of K consecutive samples with the trace kept
+        live: truncated backpropagation through time over the plastic trace.
+
+        xs [K,B,C,N,N] and ts [K,B,N,N] (or lists of K); K forwards carry the trace with its
+        gradient path, loss = mean_k BCE_k, one backward, one Adam and StepLR step.  Returns
+        (losses [K], hebb), detached: the trace is cut at the episode boundary.  Needs a net built
+        with trace_grad=True; eta is learned.  Always eager (graph=True does not apply).
+
+        The K backward nodes of a parameter all run before autograd sets .grad, so the flat
+        gradient buffer's sinks are off for the episode (every node returns a fresh tensor and
+        autograd accumulates them) and the overlapped reducer is not armed; under data parallelism
+        the gradients, eta's included, are averaged after the backward."""
+        if not getattr(self.net, "trace_grad", False):
+            raise ValueError("step_episode needs a net built with trace_grad=True")
+        if len(xs) != len(ts) or len(xs) == 0:
+            raise ValueError("step_episode: xs and ts must hold the same number (>= 1) of samples")
+        for p in self.params:
+            p.grad = None
+        trunk = self.net._trunk_plan() if hasattr(self.net, "_trunk_plan") else None
+        saved = trunk.gradbuf if trunk is not None else None
+        if trunk is not None:
+            trunk.gradbuf = None
+        try:
+            h = hebb.detach()
+            losses = []
+            for k in range(len(xs)):
+                y, h = self.net(xs[k], h)
+                losses.append(bce_loss(y, ts[k]))
+            (torch.stack(losses).sum() / len(losses)).backward()
+        finally:
+            if trunk is not None:
+                trunk.gradbuf = saved
+        if self.distributed:
+            dp.allreduce_grads(self.params, None)
+        self.opt.step()
+        self.sched.step()
+        return torch.stack([l.detach() for l in losses]), h.detach()
+
     def _eager_step(self, x, t, hebb):
         for p in self.params:
             p.grad = None

@@ -20,6 +20,24 @@ def fused_head_ok(feat_channels, nbf, seq=False):
     return FUSE_OUTCONV and not seq and feat_channels % 4 == 0 and nbf % 16 == 0 and 16 <= nbf <= 512
 
 
+_NO_TRACE_GRAD = ("backpropagation through the updated plastic trace is not supported: the "
+                  "reference detaches it before reuse (src/train.py:99)")
+
+
+def _trace_backward(ctx, X, H, w, alpha, eta, y, dy, dhn, need_dx, need_w, need_a, need_h, need_eta):
+    """The trace_grad backward of both head nodes (pu_plastic_bwd_trace): a gradient arrived for
+    H' (dhn) and / or the incoming H wants one.  Returns (dx, dw, dalpha, dH, deta), each None
+    where not wanted.  The gradient-buffer sinks are never used here: in an unrolled episode
+    several nodes of one parameter run before autograd sets .grad, so each returns a fresh tensor
+    and autograd accumulates them."""
+    dy = None if dy is None else dy.contiguous()
+    dhn = None if dhn is None else dhn.contiguous()
+    dx, dw, da, dh, deta = K.plastic_bwd_trace(X, H, w, alpha, eta, y, dy, dhn, ctx.rule, need_dx=need_dx,
+                                               need_dw=need_w or need_a, need_dh=need_h)
+    return (dx, dw if need_w else None, da if need_a else None, dh,
+            deta if need_eta and dhn is not None else None)
+
+
 class FusedHeadFunction(torch.autograd.Function):
     """(feat [B,N,N,C], outc weight [1,C,1,1], outc bias [1], H [B,N,N], w, alpha, eta) -> (Y, H').
 
@@ -28,29 +46,38 @@ class FusedHeadFunction(torch.autograd.Function):
     then the outconv backward (ReLU mask of feat fused), handing the trunk dL/d(pre-ReLU)."""
 
     @staticmethod
-    def forward(ctx, feat, wo, bo, H, w, alpha, eta, rule, update_trace, sink=None):
+    def forward(ctx, feat, wo, bo, H, w, alpha, eta, rule, update_trace, sink=None, trace_grad=False):
         # sink: optional (GradBuffer, w, alpha, outc weight, outc bias) - grads into its views
+        # trace_grad: H' keeps its gradient path (H and eta become differentiable inputs)
         ctx.sink = sink
+        ctx.trace_grad = bool(trace_grad)
+        ctx.rule = rule
         feat = feat.contiguous()
         H = H.detach().contiguous()
         wod = wo.detach().reshape(-1)
         X, y, hn = K.plastic_head_fwd(feat, wod, bo.detach(), H, w.detach(), alpha.detach(), eta.detach(), rule,
                                       update_trace)
-        ctx.save_for_backward(feat, wod, X, H, w.detach(), alpha.detach(), y)
+        ctx.save_for_backward(feat, wod, X, H, w.detach(), alpha.detach(), y, eta.detach())
         ctx.wo_shape = wo.shape
         ctx.set_materialize_grads(False)
-        if hn is not None:
+        if hn is not None and not ctx.trace_grad:
             ctx.mark_non_differentiable(hn)
         return y, hn
 
     @staticmethod
     def backward(ctx, dy, dhn):
+        if ctx.trace_grad and (dhn is not None or (dy is not None and ctx.needs_input_grad[3])):
+            feat, wod, X, H, w, alpha, y, eta = ctx.saved_tensors
+            dx, dw, da, dh, deta = _trace_backward(ctx, X, H, w, alpha, eta, y, dy, dhn, True,
+                                                   ctx.needs_input_grad[4], ctx.needs_input_grad[5],
+                                                   ctx.needs_input_grad[3], ctx.needs_input_grad[6])
+            dfeat, dwo, dbo = K.outconv_bwd(feat, wod, dx, relu_mask=True)
+            return (dfeat, dwo.view(ctx.wo_shape), dbo, dh, dw, da, deta, None, None, None, None)
         if dhn is not None:
-            raise RuntimeError("backpropagation through the updated plastic trace is not supported: the "
-                               "reference detaches it before reuse (src/train.py:99)")
+            raise RuntimeError(_NO_TRACE_GRAD)
         if dy is None:
-            return (None,) * 10
-        feat, wod, X, H, w, alpha, y = ctx.saved_tensors
+            return (None,) * 11
+        feat, wod, X, H, w, alpha, y, _ = ctx.saved_tensors
         need_dw = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
         out_h = out_o = None
         if ctx.sink is not None:
@@ -66,37 +93,48 @@ class FusedHeadFunction(torch.autograd.Function):
         if out_o is not None:
             ctx.sink[0].ready(ctx.sink[3], ctx.sink[4])
         return (dfeat, dwo.view(ctx.wo_shape), dbo, None, dw if ctx.needs_input_grad[4] else None,
-                da if ctx.needs_input_grad[5] else None, None, None, None, None)
+                da if ctx.needs_input_grad[5] else None, None, None, None, None, None)
 
 
 class PlasticHeadFunction(torch.autograd.Function):
     """(X [B,N,N], H [B,N,N], w, alpha, eta) -> (Y, H').
 
-    H' is returned without a gradient path (the reference's callers always detach it before the
-    next sample, train.py:99, and no loss depends on it), so eta receives no gradient (S3).
+    By default H' is returned without a gradient path (the reference's callers always detach it
+    before the next sample, train.py:99, and no loss depends on it), so eta receives no gradient
+    (S3).  trace_grad=True keeps the path the reference's forward leaves open: H' is
+    differentiable, H and eta receive gradients (pu_plastic_bwd_trace) whenever a gradient reaches
+    H' or the incoming H wants one; otherwise the backward is the default one, bit for bit.
     """
 
     @staticmethod
-    def forward(ctx, X, H, w, alpha, eta, rule, update_trace, sink=None):
+    def forward(ctx, X, H, w, alpha, eta, rule, update_trace, sink=None, trace_grad=False):
         # sink: optional (GradBuffer, w_param, alpha_param) - write dw/dalpha into its views
+        # trace_grad: H' keeps its gradient path (H and eta become differentiable inputs)
         ctx.sink = sink
+        ctx.trace_grad = bool(trace_grad)
+        ctx.rule = rule
         X = X.contiguous()
         H = H.detach().contiguous()
         y, hn = K.plastic_fwd(X, H, w.detach(), alpha.detach(), eta.detach(), rule, update_trace)
-        ctx.save_for_backward(X, H, w.detach(), alpha.detach(), y)
+        ctx.save_for_backward(X, H, w.detach(), alpha.detach(), y, eta.detach())
         ctx.set_materialize_grads(False)
-        if hn is not None:
+        if hn is not None and not ctx.trace_grad:
             ctx.mark_non_differentiable(hn)
         return y, hn
 
     @staticmethod
     def backward(ctx, dy, dhn):
+        if ctx.trace_grad and (dhn is not None or (dy is not None and ctx.needs_input_grad[1])):
+            X, H, w, alpha, y, eta = ctx.saved_tensors
+            dx, dw, da, dh, deta = _trace_backward(ctx, X, H, w, alpha, eta, y, dy, dhn, ctx.needs_input_grad[0],
+                                                   ctx.needs_input_grad[2], ctx.needs_input_grad[3],
+                                                   ctx.needs_input_grad[1], ctx.needs_input_grad[4])
+            return (dx, dh, dw, da, deta, None, None, None, None)
         if dhn is not None:
-            raise RuntimeError("backpropagation through the updated plastic trace is not supported: the "
-                               "reference detaches it before reuse (src/train.py:99)")
+            raise RuntimeError(_NO_TRACE_GRAD)
         if dy is None:
-            return (None,) * 8
-        X, H, w, alpha, y = ctx.saved_tensors
+            return (None,) * 9
+        X, H, w, alpha, y, _ = ctx.saved_tensors
         need_dx = ctx.needs_input_grad[0]
         need_dw = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
         out = None
@@ -108,7 +146,7 @@ class PlasticHeadFunction(torch.autograd.Function):
         if out is not None:
             ctx.sink[0].ready(ctx.sink[1], ctx.sink[2])
         return (dx, None, dw if ctx.needs_input_grad[2] else None, da if ctx.needs_input_grad[3] else None,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
 class SequentialHeadFunction(torch.autograd.Function):
@@ -141,8 +179,7 @@ class SequentialHeadFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dhn):
         if dhn is not None:
-            raise RuntimeError("backpropagation through the updated plastic trace is not supported: the "
-                               "reference detaches it before reuse (src/train.py:99)")
+            raise RuntimeError(_NO_TRACE_GRAD + "; trace gradients (trace_grad=True) need hebb_mode='slots'")
         if dy is None:
             return (None,) * 7
         X, Hs, w, alpha, y = ctx.saved_tensors

@@ -9,12 +9,13 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (ConvArgs, WgradArgs, PlasticArgs, PlasticHeadArgs, PlasticBwdArgs, AdamTensor, PackJob, WinoJob, check,
+from ._lib import (ConvArgs, WgradArgs, PlasticArgs, PlasticHeadArgs, PlasticBwdArgs, PlasticBwdTraceArgs, AdamTensor,
+                   PackJob, WinoJob, check,
                    PU_EPI_RELU, PU_EPI_ACCUM, PU_EPI_SHUFFLE2, PU_EPI_RESID, PU_CONV_NO_HALO, PU_CONV_HALO_V1,
                    PU_CONV_NO_SMALLX6, PU_EPI_OUT_BF16)
 
 __all__ = ["KernelProfiler", "igemm", "wgrad", "pack_weight", "nchw_to_nhwc", "maxpool2_fwd", "maxpool2_bwd",
-           "outconv_fwd", "outconv_bwd", "plastic_fwd", "trace_update", "plastic_bwd", "bce_fwd",
+           "outconv_fwd", "outconv_bwd", "plastic_fwd", "trace_update", "plastic_bwd", "plastic_bwd_trace", "bce_fwd",
            "bce_bwd", "adam_multi", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
 
 
@@ -669,6 +670,40 @@ def plastic_bwd(x, hebb, w, alpha, y, dy, need_dx=True, need_dw=True, out=None):
     with _Rec("plastic_bwd", flops=4.0 * B * N ** 3):
         check(L.pu_plastic_bwd(ctypes.byref(a), _p(ws), nbytes if need_dw else 0, _stream()), "pu_plastic_bwd")
     return dx, dw, da
+
+
+def plastic_bwd_trace_bytes(B, N, has_p=True, need_dh=True):
+    """HBM floor of pu_plastic_bwd_trace beyond the head backward: P and H read once by the trace
+    backward (8 B N^2), P, T_b, alpha in and dH out for the dH finish (16 B N^2)."""
+    return (8.0 * B * N * N if has_p else 0.0) + (16.0 * B * N * N if need_dh else 0.0)
+
+
+def plastic_bwd_trace(x, hebb, w, alpha, eta, y, dy, dhebb_out, rule, need_dx=True, need_dw=True, need_dh=True):
+    """The head backward with the gradient of the updated trace (pu_plastic_bwd_trace).
+
+    dy [B,N,N] or None (zeros), dhebb_out = dL/dH' [B,N,N] or None -> (dx, dw, dalpha, dhebb, deta);
+    outputs not asked for are None, deta [1] is None without dhebb_out."""
+    for t, nm in ((x, "x"), (hebb, "hebb"), (w, "w"), (alpha, "alpha"), (eta, "eta"), (y, "y"), (dy, "dy"),
+                  (dhebb_out, "dhebb_out")):
+        _req(t, nm)
+    if dy is None and dhebb_out is None:
+        raise ValueError("plastic_bwd_trace: neither dy nor dhebb_out")
+    B, N, _ = x.shape
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(w) if need_dw else None
+    da = torch.empty_like(alpha) if need_dw else None
+    dh = torch.empty_like(hebb) if need_dh else None
+    deta = torch.empty_like(eta) if dhebb_out is not None else None
+    L = lib()
+    nbytes = L.pu_plastic_bwd_trace_workspace_bytes(B, N)
+    ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=x.device)
+    a = PlasticBwdTraceArgs(B, N, rule, x.data_ptr(), hebb.data_ptr(), w.data_ptr(), alpha.data_ptr(), eta.data_ptr(),
+                            y.data_ptr(), _p(dy), _p(dhebb_out), _p(dx), _p(dw), _p(da), _p(dh), _p(deta))
+    head = 4.0 * (5 * B * N * N + 2 * N * N) + (8.0 * B * N * N + 8.0 * N * N if need_dw or need_dh else 0.0)
+    with _Rec("plastic_bwd_trace", flops=4.0 * B * N ** 3 + 8.0 * B * N * N,
+              nbytes=head + plastic_bwd_trace_bytes(B, N, dhebb_out is not None, need_dh)):
+        check(L.pu_plastic_bwd_trace(ctypes.byref(a), ws.data_ptr(), nbytes, _stream()), "pu_plastic_bwd_trace")
+    return dx, dw, da, dh, deta
 
 
 def bce_fwd(y, t):

@@ -9,6 +9,8 @@ save checkpoints (:153-203).  Differences, all opt-in:
   --batch-norm / --bilinear  the reference constructor flags batch_norm / bilinear_upsample
   --model-type     unetpres (reference default) | unetp, with --depth/--base-ch for UNetp
   --synthetic N / --dataset FILE.npz   input data besides --data DIR (the TGS PNG layout, utils/data_set.py)
+  --bptt K         episodes of K consecutive batches with the plastic trace kept live: one backward
+                   through the K trace updates (truncated BPTT), one Adam step per episode; eta learns
   --resident       keep the whole training set in HBM; default: batches stream host -> HBM through
                    pinned, double-buffered asynchronous copies (punet/loader.py) under the previous step
 Data-parallel training: launch with torch.distributed.run; each rank trains its contiguous shard
@@ -58,6 +60,9 @@ def train(net, X_train, X_val, y_train, y_val, params):
         print("Validation labels shape:", y_val.shape)
         print(params)
     bs = int(params.get("batch_size", 1))
+    bptt = int(params.get("bptt", 0))
+    if bptt and not getattr(net, "trace_grad", False):
+        raise ValueError("bptt > 0 needs a net built with trace_grad=True")
     device = params["device"]
     all_losses, val_train_losses, val_test_losses, val_accuracies = [], [], [], []
     samples_count = len(X_train)
@@ -83,8 +88,30 @@ def train(net, X_train, X_val, y_train, y_val, params):
         # trace reset per epoch (train.py:88): per-slot traces, or one trace threaded through
         hebb = net.initialZeroHebb() if seq else net.initialZeroHebb(bs)
         losses_dev = []
+        episode = []
+
+        def run_episode(hebb):
+            # K consecutive full batches, the trace live across them (truncated BPTT); the copies
+            # keep the batches alive while the prefetcher refills its slots
+            losses, h = trainer.step_episode([e[0] for e in episode], [e[1] for e in episode], hebb)
+            losses_dev.extend(losses.unbind(0))
+            episode.clear()
+            return h
+
         for (lo, hi), (x, yb) in zip(ranges, batches):
             t = yb.reshape(hi - lo, -1)
+            if bptt and hi - lo == bs:
+                episode.append((x.clone(), t.clone()))
+                if len(episode) == bptt:
+                    hebb = run_episode(hebb)
+                continue
+            if bptt:
+                # a ragged last batch: finish the open episode, then an episode of its own
+                if episode:
+                    hebb = run_episode(hebb)
+                losses, _ = trainer.step_episode([x], [t], hebb[: hi - lo])
+                losses_dev.extend(losses.unbind(0))
+                continue
             if seq:
                 loss, hebb = trainer.step(x, t, hebb)
             else:
@@ -93,6 +120,8 @@ def train(net, X_train, X_val, y_train, y_val, params):
                 if hi - lo == bs:
                     hebb = h
             losses_dev.append(loss)
+        if episode:             # the epoch's tail episode may be shorter
+            hebb = run_episode(hebb)
         # one host sync per epoch instead of loss.item() per sample (train.py:106)
         epoch_losses = torch.stack(losses_dev).cpu().tolist() if losses_dev else []
         all_losses.extend(epoch_losses)
@@ -140,7 +169,7 @@ def start_train(x_train, x_valid, y_train, y_valid, out_dir, model, img_width, i
                 max_train_time=-1, load=False, gpu=True, epochs=5, lr=3e-5, val_ratio=0.05, val_every=50,
                 save_every=100, gamma=0.666, steplr=1e6, rollout=50000, prule="hebb", debug=False,
                 model_type="unetpres", depth=5, base_ch=8, neurons=16, batch_size=1, hebb_mode="slots",
-                batch_norm=False, bilinear_upsample=False, prefetch=True):
+                batch_norm=False, bilinear_upsample=False, prefetch=True, bptt=0):
     world, rank, local = dp.init_from_env()
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
@@ -148,15 +177,16 @@ def start_train(x_train, x_valid, y_train, y_valid, out_dir, model, img_width, i
     params = {"out_dir": out_dir, "device": device, "epochs": epochs, "stop_time": stop_time, "lr": lr,
               "val_ratio": val_ratio, "val_every": val_every, "save_every": save_every, "rollout": rollout,
               "gamma": gamma, "steplr": steplr, "prule": prule, "im_width": img_width, "im_height": img_height,
-              "im_chan": img_chan, "debug": debug, "batch_size": batch_size, "prefetch": prefetch}
+              "im_chan": img_chan, "debug": debug, "batch_size": batch_size, "prefetch": prefetch,
+              "bptt": bptt}
     if model_type == "unetp":
         net = UNetp(n_channels=img_chan, n_classes=1, nbf=img_width, batch_norm=batch_norm,
                     bilinear_upsample=bilinear_upsample, device=device, rule=prule, depth=depth, base_ch=base_ch,
-                    hebb_mode=hebb_mode)
+                    hebb_mode=hebb_mode, trace_grad=bptt > 0)
     else:
         net = UNetpRes(n_channels=img_chan, n_classes=1, nbf=img_width, batch_norm=batch_norm,
                        bilinear_upsample=bilinear_upsample, device=device, rule=prule, neurons=neurons,
-                       hebb_mode=hebb_mode)
+                       hebb_mode=hebb_mode, trace_grad=bptt > 0)
     if load:
         net.load_state_dict(torch.load(model, weights_only=True))
         net.to(device)
@@ -202,6 +232,9 @@ def parse_args(argv=None):
                       help="slots: one trace per batch slot; sequential: one trace threaded through the batch")
     parser.add_option('--batch-norm', dest='batch_norm', action='store_true', default=False)
     parser.add_option('--bilinear', dest='bilinear', action='store_true', default=False)
+    parser.add_option('--bptt', dest='bptt', type='int', default=0,
+                      help='K > 0: train on episodes of K consecutive batches with the plastic trace kept live '
+                           '(truncated backpropagation through time; eta is learned); 0: the reference loop')
     parser.add_option('--seed', dest='seed', type='int', default=0)
     parser.add_option('--resident', dest='resident', action='store_true', default=False,
                       help='copy the whole training set to HBM once instead of streaming batches')
@@ -239,4 +272,5 @@ if __name__ == '__main__':
                 prule=args.prule, img_width=args.img_size, img_height=args.img_size, img_chan=1,
                 debug=args.debug, model_type=args.model_type, depth=args.depth, base_ch=args.base_ch,
                 neurons=args.neurons, batch_size=args.batch_size, hebb_mode=args.hebb_mode,
-                batch_norm=args.batch_norm, bilinear_upsample=args.bilinear, prefetch=not args.resident)
+                batch_norm=args.batch_norm, bilinear_upsample=args.bilinear, prefetch=not args.resident,
+                bptt=args.bptt)

@@ -38,8 +38,9 @@ class CoordConvUNetp(nn.Module):
     up_first = True      # concat order of the up stages: [upsampled | skip]
 
     def __init__(self, n_channels, n_classes, device, alfa_type='free', rule='hebb', nbf=256, base_ch=8,
-                 with_r=True, depth=5):
+                 with_r=True, depth=5, trace_grad=False):
         super().__init__()
+        self.trace_grad = bool(trace_grad)      # a plain attribute: not part of the state_dict
         self.n_classes = n_classes
         self.n_channels = n_channels
         self.nbf = nbf
@@ -107,10 +108,11 @@ class CoordConvUNetp(nn.Module):
         if trunk.fused_head:
             sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha, wo, bo)
             Y, Hn = FusedHeadFunction.apply(logits, wo, bo, H, self.w, self.alpha, self.eta, RULES[self.rule], True,
-                                            sink)
+                                            sink, self.trace_grad)
             return (Y[0], Hn[0]) if single else (Y, Hn)
         sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha)
-        Y, Hn = PlasticHeadFunction.apply(logits, H, self.w, self.alpha, self.eta, RULES[self.rule], True, sink)
+        Y, Hn = PlasticHeadFunction.apply(logits, H, self.w, self.alpha, self.eta, RULES[self.rule], True, sink,
+                                          self.trace_grad)
         if single:
             return Y[0], Hn[0]
         return Y, Hn

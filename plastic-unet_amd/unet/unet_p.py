@@ -94,11 +94,14 @@ def _check_gpu_tensor(t, what):
 
 class UNetp(nn.Module):
     def __init__(self, n_channels, n_classes, device, alfa_type='free', rule='hebb', nbf=128, batch_norm=False,
-                 bilinear_upsample=False, depth=5, base_ch=8, precision='fp32', hebb_mode='slots'):
+                 bilinear_upsample=False, depth=5, base_ch=8, precision='fp32', hebb_mode='slots', trace_grad=False):
         super().__init__()
         if hebb_mode not in ("slots", "sequential"):
             raise ValueError("hebb_mode must be 'slots' or 'sequential'")
         self.hebb_mode = hebb_mode
+        if trace_grad and hebb_mode == "sequential":
+            raise ValueError("trace_grad=True needs hebb_mode='slots' (the sequential head keeps its traces detached)")
+        self.trace_grad = bool(trace_grad)      # a plain attribute: not part of the state_dict
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
         if precision == "bf16" and base_ch % 32:
@@ -179,14 +182,15 @@ class UNetp(nn.Module):
         if trunk.fused_head:
             sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha, wo, bo)
             Y, Hn = FusedHeadFunction.apply(logits, wo, bo, H, self.w, self.alpha, self.eta, RULES[self.rule], True,
-                                            sink)
+                                            sink, self.trace_grad)
             return (Y[0], Hn[0]) if single else (Y, Hn)
         sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha)
         if seq:
             from punet.head import SequentialHeadFunction
             Y, Hn = SequentialHeadFunction.apply(logits, hebb, self.w, self.alpha, self.eta, RULES[self.rule], sink)
             return (Y[0], Hn) if B == 1 else (Y, Hn)
-        Y, Hn = PlasticHeadFunction.apply(logits, H, self.w, self.alpha, self.eta, RULES[self.rule], True, sink)
+        Y, Hn = PlasticHeadFunction.apply(logits, H, self.w, self.alpha, self.eta, RULES[self.rule], True, sink,
+                                          self.trace_grad)
         if single:
             return Y[0], Hn[0]
         return Y, Hn

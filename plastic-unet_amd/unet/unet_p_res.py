@@ -71,11 +71,14 @@ class up(nn.Module):  # unet_p_res.py:200-220
 
 class UNetpRes(nn.Module):
     def __init__(self, n_channels, n_classes, device, neurons=16, dropout_ratio=0.5, alfa_type='free', rule='hebb',
-                 nbf=128, batch_norm=False, bilinear_upsample=False, hebb_mode='slots'):
+                 nbf=128, batch_norm=False, bilinear_upsample=False, hebb_mode='slots', trace_grad=False):
         super().__init__()
         if hebb_mode not in ("slots", "sequential"):
             raise ValueError("hebb_mode must be 'slots' or 'sequential'")
         self.hebb_mode = hebb_mode
+        if trace_grad and hebb_mode == "sequential":
+            raise ValueError("trace_grad=True needs hebb_mode='slots' (the sequential head keeps its traces detached)")
+        self.trace_grad = bool(trace_grad)      # a plain attribute: not part of the state_dict
         self.n_classes = n_classes
         self.n_channels = n_channels
         self.nbf = nbf
@@ -153,14 +156,15 @@ class UNetpRes(nn.Module):
         if trunk.fused_head:
             sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha, wo, bo)
             Y, Hn = FusedHeadFunction.apply(logits, wo, bo, H, self.w, self.alpha, self.eta, RULES[self.rule], True,
-                                            sink)
+                                            sink, self.trace_grad)
             return (Y[0], Hn[0]) if single else (Y, Hn)
         sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha)
         if seq:
             from punet.head import SequentialHeadFunction
             Y, Hn = SequentialHeadFunction.apply(logits, hebb, self.w, self.alpha, self.eta, RULES[self.rule], sink)
             return (Y[0], Hn) if B == 1 else (Y, Hn)
-        Y, Hn = PlasticHeadFunction.apply(logits, H, self.w, self.alpha, self.eta, RULES[self.rule], True, sink)
+        Y, Hn = PlasticHeadFunction.apply(logits, H, self.w, self.alpha, self.eta, RULES[self.rule], True, sink,
+                                          self.trace_grad)
         if single:
             return Y[0], Hn[0]
         return Y, Hn

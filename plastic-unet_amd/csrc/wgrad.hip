@@ -1161,6 +1161,321 @@ __global__ __launch_bounds__(512) void wgrad_wino_x6_kernel(const WinoWgradParam
     }
 }
 
+// ---------------------------------- Winograd-domain weight gradient, one position column per block
+// wgrad_wino_x6_kernel forms dW = G^T M G rows first: R[r][j] = sum_a G[a][r] M[a][j] is local to
+// the wave that holds column j's four positions, and only the second half, dW[r][s] = sum_j R[r][j]
+// G[j][s], crosses waves.  So a block may own ONE column j of the 4 x 4 positions and hand phase 2
+// the three numbers R[0..2][j] per (n, c): with the same 65 536 accumulators it then covers 128 input
+// x 128 output channels and forms 4 x (128 + 128) values per tile for 4 x 128 x 128 products - 64
+// products per formed value against 32.  The slab page of (split z, column j) is virtual split
+// 4 z + j: [Nr][Kcp] with Kc = 3 C (+ 1 bias column) and column r C + c; wgrad_finish_cols_kernel
+// finishes the transform per split in fp32 and sums the splits.  Every value is formed by the
+// operations of wgrad_wino_x6_kernel in its order (transforms, split, products, accumulation per
+// split over the same tile ranges, R, then P0 + P1, then the fp64 sums), so dweight and dbias are
+// bit-identical to that kernel's.
+//
+// 512 threads, 8 waves (wc of 2, wn of 4): a wave accumulates 64 input x 32 output channels for
+// the column's 4 positions (8 accumulator blocks).  A stage is 16 tiles = one k-step, in two
+// sub-stages of two positions (i = 2 h, 2 h + 1), so the LDS footprint is that of the 64 x 64
+// kernel: per operand and slot 2 positions x 3 planes x [16 tile rows][128 channels] bf16 (256-byte
+// rows, wgrad_bf16_kernel's swizzle).  Thread (tile pt, channel quad cq) holds the two window
+// columns (4 rows each) that column j of B^T d B reads and the one or two dZ columns that column j
+// of A' e A'^T reads.  The column is a block-uniform run-time value (all four columns of a
+// (cx, ny, z) sit next to each other in ONE grid and share their windows in L2); each window
+// column gets the row transform t_i first, as in the 64 x 64 kernel, then the two columns combine
+// in a packed fma with a +-1 operand - exactly the rounded sum or difference:
+//     j = 0: t[0] - t[2]   j = 1: t[1] + t[2]   j = 2: t[2] - t[1]   j = 3: t[1] - t[3]
+//     j = 0: u[0]          j = 1: u[0] + u[1]   j = 2: u[0] - u[1]   j = 3: u[1] (= -A row 3)
+// (j = 2 loads its columns as (2, 1): forming t[1] - t[2] and negating M afterwards is NOT
+// bit-identical - the MFMA accumulation is not symmetric under a sign flip of an operand.)
+// Sub-stage (k, 1) forms all four positions' values of stage k + 1 (positions 2, 3 are held in
+// registers for sub-stage (k + 1, 0)), after which the raw columns are dead and stage k + 2's are
+// loaded: two sub-stages of cover, as in the 64 x 64 kernel.
+// Requires wino_wgrad_ok and c0 % 128 == c1 % 128 == N % 128 == 0.
+constexpr int WWR_IMG = 16 * 256;            // one (position, plane) image: 16 tile rows x 128 channels
+constexpr int WWR_SLOT = 2 * 3 * WWR_IMG;    // one operand, one sub-stage: 2 positions x 3 planes
+__device__ __forceinline__ int wwr_off(int row, int col) {   // byte offset in a 128-column plane
+    return row * 256 + 16 * ((col >> 3) ^ wb_sw(row)) + 2 * (col & 7);
+}
+
+__global__ __launch_bounds__(512) void wgrad_wino_cols_x6_kernel(const WinoWgradParams w) {
+#pragma clang fp contract(off)
+    const WgradParams& p = w.p;
+    // two sub-stage slots per operand as separate arrays (see wgrad_wino_x6_kernel)
+    __shared__ __attribute__((aligned(16))) char lx0[WWR_SLOT];
+    __shared__ __attribute__((aligned(16))) char lx1[WWR_SLOT];
+    __shared__ __attribute__((aligned(16))) char lg0[WWR_SLOT];
+    __shared__ __attribute__((aligned(16))) char lg1[WWR_SLOT];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wc = wave & 1, wn = wave >> 1;
+    // logical block (split z, output block ny, input block cx, column J), J fastest: the four columns
+    // of a channel block and tile range run on one XCD and read the same windows and dZ tiles
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
+    const int J = blk & 3;
+    const int cx = (blk >> 2) % p.gx;
+    const int rest = (blk >> 2) / p.gx;
+    const int ny = rest % p.gy;
+    const int z = rest / p.gy;
+    const int t_begin = z * w.tps;
+    const int t_end = min(w.tiles, t_begin + w.tps);
+    const int S = (t_end - t_begin + 15) >> 4;
+    const int xca = J == 0 ? 0 : J == 2 ? 2 : 1, xcb = J == 3 ? 3 : J == 2 ? 1 : 2;   // window columns a, b: dv = t_a + sx t_b
+    const float sxf = J == 1 ? 1.f : -1.f;
+    const int gca = J == 3 ? 1 : 0;                           // dZ columns: ev = u_a + sg u_b, b = column 1
+    const bool gtwo = J == 1 || J == 2;                       // (columns 0 and 3 read one dZ column)
+    const float sgf = J == 2 ? -1.f : 1.f;
+    const wg_f32x2 sx2 = {sxf, sxf}, sg2 = {sgf, sgf};
+
+    // ---- producer role: tile pt of a stage, channel quad cq of the 128 input / output channels
+    const int pt = tid >> 5, cq = tid & 31;
+    const int c_lo = cx * 128;
+    const bool first = c_lo < p.c0;
+    const int cs = first ? p.c0 : p.c1;       // pixel stride of the input block's source
+    const int shift = p.Wi + 1;               // window corner (2ty-1, 2tx-1) >= (-1, -1)
+    const __amdgpu_buffer_rsrc_t xr = ww_rsrc((first ? p.src0 : p.src1) - (long long)shift * cs,
+                                              first ? w.x0_bytes : w.x1_bytes);
+    const __amdgpu_buffer_rsrc_t gr = ww_rsrc(p.P, w.p_bytes);
+    const unsigned pixb = (unsigned)cs * 4u;
+    const unsigned xco = (unsigned)((first ? c_lo : c_lo - p.c0) + 4 * cq) * 4u;
+    const unsigned gco = (unsigned)(ny * 128 + 4 * cq) * 4u;
+    const unsigned gpix = (unsigned)p.N * 4u;
+    const int st_off = wwr_off(pt, 4 * cq);   // the thread's 8-byte slot in every image
+
+    wg_f32x2 da[4][2], db[4][2], ea[2][2], eb[2][2];   // raw columns a, b: [window / dZ row][channel pair]
+    // decode tile pt of stage k and load its columns (out-of-range tiles, rows and columns: zeros)
+    auto load_stage = [&](int k) {
+        const int m = t_begin + 16 * k + pt;
+        const bool mv = m < t_end;
+        int ty = 0, tx = 0, b = 0;
+        if (mv) {
+            const int t2 = fdiv(m, w.dTw);
+            tx = m - t2 * (p.Wo >> 1);
+            b = fdiv(t2, w.dTh);
+            ty = t2 - b * (p.Ho >> 1);
+        }
+        const int y0 = 2 * ty - 1, x0 = 2 * tx - 1;
+        const unsigned base = (unsigned)(((b * p.Hi + y0) * p.Wi + x0 + shift) * cs) * 4u + xco;
+        // columns 1 and 2 are always inside the (even-width) image
+        const bool cva = mv && (xca != 0 || x0 >= 0), cvb = mv && (xcb != 3 || x0 + 3 < p.Wi);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const bool rv = (unsigned)(y0 + r) < (unsigned)p.Hi;
+            const unsigned oa = cva && rv ? base + (unsigned)xca * pixb : LEAN_OOB;
+            const unsigned ob = cvb && rv ? base + (unsigned)xcb * pixb : LEAN_OOB;
+            const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)(r * p.Wi) * pixb);
+            const f32x4 a4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, oa, so, 0));
+            const f32x4 b4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, ob, so, 0));
+            da[r][0] = wg_f32x2{a4[0], a4[1]}; da[r][1] = wg_f32x2{a4[2], a4[3]};
+            db[r][0] = wg_f32x2{b4[0], b4[1]}; db[r][1] = wg_f32x2{b4[2], b4[3]};
+        }
+        const unsigned gbase = (unsigned)((b * p.Ho + 2 * ty) * p.Wo + 2 * tx) * gpix + gco;
+        const unsigned ga_ = mv ? gbase + (unsigned)gca * gpix : LEAN_OOB;
+        const unsigned gb_ = mv && gtwo ? gbase + gpix : LEAN_OOB;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)(a * p.Wo) * gpix);
+            const f32x4 a4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gr, ga_, so, 0));
+            const f32x4 b4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gr, gb_, so, 0));
+            ea[a][0] = wg_f32x2{a4[0], a4[1]}; ea[a][1] = wg_f32x2{a4[2], a4[3]};
+            eb[a][0] = wg_f32x2{b4[0], b4[1]}; eb[a][1] = wg_f32x2{b4[2], b4[3]};
+        }
+    };
+    // one position's 4 channels of both operands -> hi / mid / lo plane words of slot position jj
+    auto put = [&](const wg_f32x2 (&v)[2], char* b) {
+        unsigned h0, m0, l0, h1, m1, l1;
+        ww_split(v[0], h0, m0, l0);
+        ww_split(v[1], h1, m1, l1);
+        typedef unsigned wu32x2 __attribute__((ext_vector_type(2)));
+        *reinterpret_cast<wu32x2*>(b) = wu32x2{h0, h1};
+        *reinterpret_cast<wu32x2*>(b + WWR_IMG) = wu32x2{m0, m1};
+        *reinterpret_cast<wu32x2*>(b + 2 * WWR_IMG) = wu32x2{l0, l1};
+    };
+    wg_f32x2 hd[2][2], he[2][2];              // positions 2, 3 of the stage formed last
+    wg_f32x2 bsum[2] = {{0.f, 0.f}, {0.f, 0.f}};   // dbias partial of the thread's output quad
+    // column J of Dhat and Ehat from the raw columns, in the 64 x 64 kernel's order (the row
+    // transform of each column first, then the two columns combined): positions (0, J), (1, J) to
+    // the slot, (2, J), (3, J) held
+    auto form_a = [&](char* sx, char* sg) {
+        wg_f32x2 dv0[2], dv1[2], ev0[2], ev1[2];
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            const wg_f32x2 ta[4] = {da[0][hf] - da[2][hf], da[1][hf] + da[2][hf], da[2][hf] - da[1][hf], da[1][hf] - da[3][hf]};
+            const wg_f32x2 tb[4] = {db[0][hf] - db[2][hf], db[1][hf] + db[2][hf], db[2][hf] - db[1][hf], db[1][hf] - db[3][hf]};
+            const wg_f32x2 ua[4] = {ea[0][hf], ea[0][hf] + ea[1][hf], ea[0][hf] - ea[1][hf], ea[1][hf]};
+            const wg_f32x2 ub[4] = {eb[0][hf], eb[0][hf] + eb[1][hf], eb[0][hf] - eb[1][hf], eb[1][hf]};
+            dv0[hf] = __builtin_elementwise_fma(tb[0], sx2, ta[0]);
+            dv1[hf] = __builtin_elementwise_fma(tb[1], sx2, ta[1]);
+            hd[0][hf] = __builtin_elementwise_fma(tb[2], sx2, ta[2]);
+            hd[1][hf] = __builtin_elementwise_fma(tb[3], sx2, ta[3]);
+            ev0[hf] = __builtin_elementwise_fma(ub[0], sg2, ua[0]);
+            ev1[hf] = __builtin_elementwise_fma(ub[1], sg2, ua[1]);
+            he[0][hf] = __builtin_elementwise_fma(ub[2], sg2, ua[2]);
+            he[1][hf] = __builtin_elementwise_fma(ub[3], sg2, ua[3]);
+            bsum[hf] += ea[0][hf] + eb[0][hf];    // dZ rows 0, 1 in the 64 x 64 kernel's order (J = 1)
+            bsum[hf] += ea[1][hf] + eb[1][hf];
+        }
+        put(dv0, sx + st_off);
+        put(ev0, sg + st_off);
+        put(dv1, sx + 3 * WWR_IMG + st_off);
+        put(ev1, sg + 3 * WWR_IMG + st_off);
+    };
+    auto form_b = [&](char* sx, char* sg) {
+        put(hd[0], sx + st_off);
+        put(he[0], sg + st_off);
+        put(hd[1], sx + 3 * WWR_IMG + st_off);
+        put(he[1], sg + 3 * WWR_IMG + st_off);
+    };
+
+    // ---- MFMA role: transposed fragment reads (k = tile row); rows +0 / +4 of a fragment sit in
+    // differently swizzled rows, so each has its own offset
+    const int grp = lane >> 4, gq = (lane >> 2) & 3, gp = lane & 3;
+    const int rsub = 8 * (grp >> 1) + gq;
+    const int ccol = 16 * (grp & 1) + 4 * gp;
+    int xo[2][2], go[2];
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+        xo[0][hh] = wwr_off(rsub + 4 * hh, wc * 64 + ccol);
+        xo[1][hh] = wwr_off(rsub + 4 * hh, wc * 64 + 32 + ccol);
+        go[hh] = wwr_off(rsub + 4 * hh, wn * 32 + ccol);
+    }
+    auto tr2 = [&](const char* b, int o0, int o1) {
+        const wi16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4_t*)(b + o0));
+        const wi16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4_t*)(b + o1));
+        typedef short wi16x8 __attribute__((ext_vector_type(8)));
+        const wi16x8 av = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+        return __builtin_bit_cast(wg_bf16x8, av);
+    };
+    f32x16 acc[8];                            // [f][i]: input channels 32 f .., position (i, J)
+#pragma unroll
+    for (int x = 0; x < 8; ++x)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[x][r] = 0.f;
+    // slot position jj = position j of the row: 3 dZ fragments, then 6 products for each channel half
+    auto mma = [&](auto j_c, const char* sx, const char* sg, int jj) {
+        constexpr int j = decltype(j_c)::value;
+        const char* gb = sg + jj * 3 * WWR_IMG;
+        const wg_bf16x8 ph = tr2(gb, go[0], go[1]), pm = tr2(gb + WWR_IMG, go[0], go[1]),
+                        pl = tr2(gb + 2 * WWR_IMG, go[0], go[1]);
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const char* xb = sx + jj * 3 * WWR_IMG;
+            const wg_bf16x8 qh = tr2(xb, xo[f][0], xo[f][1]), qm = tr2(xb + WWR_IMG, xo[f][0], xo[f][1]),
+                            ql = tr2(xb + 2 * WWR_IMG, xo[f][0], xo[f][1]);
+            f32x16 c = acc[4 * f + j];
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qm, pm, c, 0, 0, 0);   // small terms first
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ql, ph, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qh, pl, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qm, ph, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qh, pm, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qh, ph, c, 0, 0, 0);
+            acc[4 * f + j] = c;
+        }
+    };
+
+    // sub-stage (k, h): the 24 MFMAs of positions 2 h, 2 h + 1 from slot h while the other slot is
+    // formed - h = 0: the held positions 2, 3 of stage k; h = 1: stage k + 1 from the raw rows,
+    // then stage k + 2's rows are loaded (past the last stage: zeros into a slot no MFMA reads)
+    auto sub = [&](int k, auto h_c) {
+        constexpr int h = decltype(h_c)::value;
+        char* sx = h ? lx1 : lx0;
+        char* sg = h ? lg1 : lg0;
+        char* nx = h ? lx0 : lx1;
+        char* ng = h ? lg0 : lg1;
+        mma(std::integral_constant<int, 2 * h>{}, sx, sg, 0);
+        if constexpr (h == 0) {
+            form_b(nx, ng);
+        } else {
+            form_a(nx, ng);
+            load_stage(k + 2);
+        }
+        mma(std::integral_constant<int, 2 * h + 1>{}, sx, sg, 1);
+        // the wave's 24 MFMAs spread over the forming work, operands fetched a channel half ahead
+#if !PU_NO_ILV
+        __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);       // position 0: dZ and half 0
+#pragma unroll
+        for (int q = 0; q < 24; ++q) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // one MFMA
+            if (q == 0 || q == 12) __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);   // half 1
+            if (q == 6) __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);             // position 1
+            __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);     // ~1/24 of the VALU
+            if (q & 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // 12 plane stores
+        }
+#endif
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");         // s_barrier is no compiler fence: keep LDS reads behind it
+    };
+
+    // prologue: stage 0 formed (positions 0, 1 in slot 0), stage 1's rows in flight
+    load_stage(0);
+    form_a(lx0, lg0);
+    load_stage(1);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    for (int k = 0; k < S; ++k) {
+        sub(k, std::integral_constant<int, 0>{});
+        sub(k, std::integral_constant<int, 1>{});
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // trailing (empty-range) loads
+
+    float* slab = p.slab + (long long)(4 * z + J) * p.Nr * p.Kcp;
+    // ---- bias: column sums of dZ over the split, fixed order (thread stages, then the 16 tiles);
+    // column 1's blocks read all four dZ pixels.  p.K is this slab's bias column, 3 C.
+    if (p.bias_mode == 1 && cx == 0 && J == 1) {
+        wg_f32x2* red = reinterpret_cast<wg_f32x2*>(lg0);
+        red[2 * tid] = bsum[0];
+        red[2 * tid + 1] = bsum[1];
+        __syncthreads();
+        if (tid < 64) {                       // channel pair tid of the 128
+            wg_f32x2 v = red[tid];
+            for (int r = 1; r < 16; ++r) v += red[r * 64 + tid];
+            slab[(long long)(ny * 128 + 2 * tid) * p.Kcp + p.K] = v[0];
+            slab[(long long)(ny * 128 + 2 * tid + 1) * p.Kcp + p.K] = v[1];
+        }
+        __syncthreads();                      // lg0 is reused below
+    }
+
+    // ---- first half of the output transform, lane local: R[r] = sum_a G[a][r] M[a][J] with
+    // M[a][J] = s_a s_J M'[a][J], the 64 x 64 kernel's expression; column r C + c of the page.
+    // An accumulator lane holds 4 channels of one output row n, so direct stores would be 32-byte
+    // pieces of 32 slab rows; each wave turns its [32 n][64 c] tile of one r through a private LDS
+    // tile (rows skewed by 16 B) and stores 4 rows x 256 contiguous bytes per instruction.
+    constexpr int TP = 68;                    // floats per staging row
+    const float kap = J == 3 ? -1.f : 1.f;
+    float* wt = reinterpret_cast<float*>((wave >> 1) == 0 ? lx0 : (wave >> 1) == 1 ? lx1 : (wave >> 1) == 2 ? lg0 : lg1) +
+                (wave & 1) * (32 * TP);
+    const int ln = lane & 31, lh = lane >> 5;
+    const int rr = lane >> 4, rc = (lane & 15) * 4;
+    float* obase = slab + (long long)(ny * 128 + wn * 32 + rr) * p.Kcp + c_lo + wc * 64 + rc;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                f32x4 t;
+#pragma unroll
+                for (int ee = 0; ee < 4; ++ee) {
+                    const int idx = 4 * q + ee;
+                    const float m0 = acc[4 * f][idx], m1 = acc[4 * f + 1][idx];
+                    const float m2 = acc[4 * f + 2][idx], m3 = -acc[4 * f + 3][idx];
+                    const float hs = 0.5f * (m1 + m2);
+                    t[ee] = kap * (r == 0 ? m0 + hs : r == 1 ? 0.5f * (m1 - m2) : hs + m3);
+                }
+                *reinterpret_cast<f32x4*>(wt + ln * TP + 32 * f + 8 * q + 4 * lh) = t;
+            }
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(wt + (rr + 4 * it) * TP + rc);
+            *reinterpret_cast<f32x4*>(obase + (long long)(4 * it) * p.Kcp + r * p.C) = v;
+        }
+    }
+}
+
 // ------------------------------------------------------- single-channel stem weight gradient
 // dW[n][tap] = sum_m dZ[m][n] x[m + tap] and db[n] = sum_m dZ[m][n] for the 1 -> N stem conv
 // (inc.c0): the layer is the read of dZ (N channels per pixel).  Blocks sweep 16 x 64 pixel tiles
@@ -1696,10 +2011,137 @@ __global__ __launch_bounds__(576) void wgrad_finish_t_kernel(const T* __restrict
     }
 }
 
+// `count` values v(0), v(1), ... in sum_chains' order: value i to chain i & 3 while
+// i < 4 * (count / 4), the remainder to chain 0, result (s0 + s1) + (s2 + s3).  v(i) returns NV quads.
+template <int NV, typename F>
+__device__ __forceinline__ void chain_values(int count, F&& v, f64x4 (&out)[NV]) {
+    f64x4 s[NV][4] = {};
+    int i = 0;
+    for (; i + 4 <= count; i += 4) {
+        f32x4 q[4][NV];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v(i + u, q[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int e = 0; e < NV; ++e) s[e][u] += widen(q[u][e]);
+    }
+    for (; i < count; ++i) {
+        f32x4 q[NV];
+        v(i, q);
+#pragma unroll
+        for (int e = 0; e < NV; ++e) s[e][0] += widen(q[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < NV; ++e) out[e] = (s[e][0] + s[e][1]) + (s[e][2] + s[e][3]);
+}
+
+// phase 2 of the column plans (wgrad_wino_cols_x6_kernel): page 4 z + j of the slab holds
+// R[r][j] = sum_a G[a][r] M[a][j] of tile split z at column r C + c, exactly the fp32 values
+// wgrad_wino_x6_kernel forms before its waves exchange halves.  This kernel finishes that kernel's
+// transform per split in fp32, in its order - P0 from columns 0, 1, P1 from columns 2, 3,
+// dW[r][s] = P0[s] + P1[s] - and sums the splits in fp64 in the order that kernel's plan would
+// take: G groups of splits g, g + G, ... in sum_chains' order, then (G > 1) the G partials again in
+// sum_chains' order; one rounding to fp32.  G is the 64 x 64 plan's group count (1 or 2 for
+// these shapes), so the result is bit-identical to wgrad_wino_x6_kernel + wgrad_reduce.
+// Block (chunk of 256 channels, row n), thread (group lane g, r, 4 channels); the partials of
+// G = 2 meet in LDS.  Transposed through LDS to the contiguous [c][3][3] run of dweight[n]:
+// float4 when `vec` (16-byte aligned dweight), scalar otherwise.  The bias is column 3 C of the
+// pages of column 1, the only blocks that read all four dZ pixels of a tile.
+__global__ __launch_bounds__(384) void wgrad_finish_cols_kernel(const float* __restrict__ slab, int zs, int G, int Nr,
+                                                                 int Kcp, int C, int bias_mode, float* __restrict__ dw,
+                                                                 float* __restrict__ db, int accumulate, int vec) {
+#pragma clang fp contract(off)
+    __shared__ float tr[256 * 9];
+    __shared__ double pp[2][9][256];
+    __shared__ double pb[2];
+    const long long total = (long long)Nr * Kcp;
+    const int n = blockIdx.y;
+    const int c0 = blockIdx.x * 256;
+    const int g = threadIdx.x / 192, t = threadIdx.x - g * 192;
+    const int r = t >> 6, cq = (t & 63) * 4;
+    const int cn = min(256, C - c0);
+    const int count = (zs - g + G - 1) / G;           // splits g, g + G, ...
+    f64x4 acc[3];
+    if (cq < cn) {
+        const float* base = slab + (long long)n * Kcp + r * C + c0 + cq;
+        chain_values<3>(count, [&](int i, f32x4 (&q)[3]) {
+            const float* pz = base + (long long)(4 * (g + i * G)) * total;
+            const f32x4 R0 = *reinterpret_cast<const f32x4*>(pz), R1 = *reinterpret_cast<const f32x4*>(pz + total);
+            const f32x4 R2 = *reinterpret_cast<const f32x4*>(pz + 2 * total), R3 = *reinterpret_cast<const f32x4*>(pz + 3 * total);
+            const f32x4 h1 = 0.5f * R1, h2 = 0.5f * R2;
+            q[0] = (R0 + h1) + h2;
+            q[1] = h1 + (-0.5f * R2);
+            q[2] = h1 + (h2 + R3);
+        }, acc);
+        if (G > 1) {
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pp[g][3 * r + s][cq + e] = acc[s][e];
+        }
+    }
+    double bacc = 0.0;
+    const bool bias_thread = bias_mode == 1 && blockIdx.x == 0 && t == 0;
+    if (bias_thread) {
+        const float* bp = slab + total + (long long)n * Kcp + 3 * C;
+        double s4[4] = {0.0, 0.0, 0.0, 0.0};
+        int i = 0;
+        for (; i + 4 <= count; i += 4)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s4[u] += (double)bp[(long long)(4 * (g + (i + u) * G)) * total];
+        for (; i < count; ++i) s4[0] += (double)bp[(long long)(4 * (g + i * G)) * total];
+        bacc = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+        if (G > 1) pb[g] = bacc;
+    }
+    __syncthreads();
+    if (g == 0) {
+        if (cq < cn) {
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    double v = acc[s][e];
+                    if (G > 1) {                      // two partials: both on chain 0
+                        double c4[4] = {0.0, 0.0, 0.0, 0.0};
+                        c4[0] += pp[0][3 * r + s][cq + e];
+                        c4[0] += pp[1][3 * r + s][cq + e];
+                        v = (c4[0] + c4[1]) + (c4[2] + c4[3]);
+                    }
+                    tr[(cq + e) * 9 + 3 * r + s] = (float)v;
+                }
+        }
+        if (bias_thread) {
+            double v = bacc;
+            if (G > 1) {
+                double c4[4] = {0.0, 0.0, 0.0, 0.0};
+                c4[0] += pb[0];
+                c4[0] += pb[1];
+                v = (c4[0] + c4[1]) + (c4[2] + c4[3]);
+            }
+            db[n] = accumulate ? db[n] + (float)v : (float)v;
+        }
+    }
+    __syncthreads();
+    float* o = dw + ((long long)n * C + c0) * 9;
+    const int run = cn * 9;
+    if (vec) {
+        for (int i = threadIdx.x * 4; i < run; i += blockDim.x * 4) {
+            f32x4 v = {tr[i], tr[i + 1], tr[i + 2], tr[i + 3]};
+            if (accumulate) v += *reinterpret_cast<const f32x4*>(o + i);
+            *reinterpret_cast<f32x4*>(o + i) = v;
+        }
+    } else {
+        for (int i = threadIdx.x; i < run; i += blockDim.x) o[i] = accumulate ? o[i] + tr[i] : tr[i];
+    }
+}
+
 struct WgradPlan {
     int BN, BK, splits, mps, Nr, Kc, Kcp, M, K, C, G, gx, gy;
     bool qvec, dma, small, halo, stem;
     bool wino = false;                        // Winograd-domain kernel (wgrad_wino_x6_kernel)
+    bool cols = false;                        // ... its one-column-per-block form (wgrad_wino_cols_x6_kernel)
+    int Gfin = 1;                             // ... the 64 x 64 plan's reduction groups, which its finisher follows
     bool pw = false;                          // pointwise small-channel kernel (wgrad_pw_kernel)
     int tiles = 0, tps = 0;
     int nt = 1;                               // halo kernel: 64-channel output tiles per block
@@ -1778,6 +2220,10 @@ static void plan_halo(const pu_wgrad_args* a, WgradPlan* pl) {
 // the Winograd-domain kernel: 3x3 / s1 / p1 on an even same-size grid, 64-channel input blocks
 // from one source each, 64-channel output blocks, the 6-product arithmetic, byte offsets of the
 // (shifted) sources and of dZ under 2^31; PU_WINO_WGRAD=0 keeps the direct kernels (A/B runs)
+// Fewest tiles at which the column plan (wgrad_wino_cols_x6_kernel) is taken: C2's smallest qualifying
+// layers (the 8 x 8 level at batch 32) have 512; the measured gate is in DESIGN.md section 2.
+constexpr int WWR_MIN_TILES = 512;
+
 static bool wino_wgrad_ok(const pu_wgrad_args* a, const WgradPlan* pl) {
     static const bool on = [] {
         const char* e = getenv("PU_WINO_WGRAD");
@@ -1859,6 +2305,38 @@ static int plan_wgrad(const pu_wgrad_args* a, WgradPlan* pl) {
         occ = 2;
     }
     pl->halo = false;
+    if (wino_wgrad_ok(a, pl) && a->c0 % 128 == 0 && a->c1 % 128 == 0 && a->n % 128 == 0 &&
+        a->batch * (a->out_h / 2) * (a->out_w / 2) >= WWR_MIN_TILES) {
+        // column plan: (C / 128) x (N / 128) channel blocks x 4 position columns x the 64 x 64 plan's
+        // tile splits, one 512-thread block per CU.  The slab has 4 pages per tile split (virtual split 4 z + j)
+        // of [Nr][3 C (+ 1 bias column)] entries: splits, Kc and Kcp describe those pages.
+        pl->wino = pl->cols = true;
+        pl->BN = 128;
+        pl->BK = 3 * 128;
+        pl->gx = pl->C / 128;
+        pl->gy = a->n / 128;
+        pl->tiles = a->batch * (a->out_h / 2) * (a->out_w / 2);
+        const int stages = ceil_div(pl->tiles, 16);
+        int zs = 256 / (4 * pl->gx * pl->gy);
+        if (zs > stages) zs = stages;
+        if (zs < 1) zs = 1;
+        pl->tps = ceil_div(stages, zs) * 16;
+        pl->splits = 4 * ceil_div(pl->tiles, pl->tps);
+        pl->mps = pl->tps * 4;
+        pl->Kc = 3 * pl->C + (a->bias_mode == 1 ? 1 : 0);
+        pl->Kcp = (pl->Kc + 3) / 4 * 4;
+        // the finisher sums the splits in the groups the 64 x 64 plan of this call would use
+        // (C, N >= 128: one or two)
+        {
+            WgradPlan q = *pl;
+            q.splits = pl->splits / 4;
+            q.Kcp = (9 * pl->C + (a->bias_mode == 1 ? 1 : 0) + 3) / 4 * 4;
+            plan_groups(&q);
+            pl->Gfin = q.G;
+        }
+        pl->G = 1;                           // no fp64 partials in the workspace
+        return PU_OK;
+    }
     if (wino_wgrad_ok(a, pl)) {
         // one 512-thread block per CU: (C / 64) x (N / 64) channel blocks x tile splits of whole
         // 16-tile stages
@@ -2355,6 +2833,13 @@ constexpr long long WR_WIDE_MAX = 16384;
 static int wgrad_reduce(const WgradPlan& pl, const pu_wgrad_args* a, void* workspace, hipStream_t s) {
     const long long total = (long long)pl.Nr * pl.Kcp;
     const float* slab = (const float*)workspace;
+    if (pl.cols) {                                    // 4 pages per tile split, combined by the finisher
+        const dim3 fg((unsigned)ceil_div(pl.C, 256), (unsigned)a->n);
+        const int vec = ((uintptr_t)a->dweight & 15) == 0;
+        hipLaunchKernelGGL(wgrad_finish_cols_kernel, fg, dim3(192 * pl.Gfin), 0, s, slab, pl.splits / 4, pl.Gfin, pl.Nr,
+                           pl.Kcp, pl.C, a->bias_mode, a->dweight, a->dbias, a->accumulate, vec);
+        return check_launch("pu_wgrad (reduce)");
+    }
     if ((pl.small || pl.stem || pl.pw || (!pl.wino && total <= WR_WIDE_MAX)) && a->bias_mode != 2) {
         hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)ceil_div(total, (long long)WR_E)), dim3(256), 0, s,
                            slab, pl.splits, total, a->n, pl.Kcp, pl.K, pl.C, a->kh, a->kw, a->bias_mode, a->dweight,
@@ -2515,7 +3000,12 @@ extern "C" int pu_wgrad_phase(const pu_wgrad_args* a, void* workspace, size_t ws
             ww.x0_bytes = (unsigned)(px * a->c0 * 4);
             ww.x1_bytes = (unsigned)(px * a->c1 * 4);
             ww.p_bytes = (unsigned)((long long)pl.M * a->n * 4);
-            hipLaunchKernelGGL(wgrad_wino_x6_kernel, grid, dim3(512), 0, s, ww);
+            if (pl.cols) {
+                ww.p.K = 3 * pl.C;            // the bias column of a row page
+                hipLaunchKernelGGL(wgrad_wino_cols_x6_kernel, grid, dim3(512), 0, s, ww);
+            } else {
+                hipLaunchKernelGGL(wgrad_wino_x6_kernel, grid, dim3(512), 0, s, ww);
+            }
         } else if (pl.halo) {
             if (pl.nt == 2) hipLaunchKernelGGL(wgrad_halo_x6_kernel<2>, grid, dim3(512), 0, s, p);
             else hipLaunchKernelGGL(wgrad_halo_x6_kernel<1>, grid, dim3(256), 0, s, p);

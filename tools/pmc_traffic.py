@@ -22,6 +22,8 @@ import sys
 def tag_of(name, grid=None):
     # the Winograd kernels: bench.py tags unsplit launches igemm<256x64,wino> (grid 256 x 512
     # threads, persistent or one block per item) and split-K ones with ",k<n>" (fewer items)
+    if "wgrad_wino_cols_x6_kernel" in name:
+        return "wgrad<128x384,wino,x6>"
     if "wgrad_wino_x6_kernel" in name:
         return "wgrad<64x576,wino,x6>"
     if "wino_x6_kernel" in name:

@@ -2988,7 +2988,7 @@ extern "C" int pu_wgrad_phase(const pu_wgrad_args* a, void* workspace, size_t ws
         else if (a->math == 1) hipLaunchKernelGGL((wgrad_dma_kernel<BN_, BK_, WN_, WK_, 3, true>), grid, dim3(256), 0, s, p); \
         else hipLaunchKernelGGL((wgrad_dma_kernel<BN_, BK_, WN_, WK_, 3, false>), grid, dim3(256), 0, s, p); \
     } while (0)
-#define PU_WG_REG(BN_, BK_, WN_, WK_, Q_) hipLaunchKernelGGL((wgrad_kernel<BN_, BK_, WN_, WK_, Q_>), grid, dim3(256), 0, s, p)
+#define PU_WG_REG(BN_, BK_, WN_, WK_) hipLaunchKernelGGL((wgrad_kernel<BN_, BK_, WN_, WK_, false>), grid, dim3(256), 0, s, p)
         if (pl.wino) {
             WinoWgradParams ww;
             ww.p = p;
@@ -3012,19 +3012,16 @@ extern "C" int pu_wgrad_phase(const pu_wgrad_args* a, void* workspace, size_t ws
         } else if (pl.dma) {
             if (pl.BK == 64) PU_WG_DMA(64, 64, 2, 2);
             else if (pl.BN == 64 && pl.BK == 128) PU_WG_DMA(64, 128, 2, 2);
-            else if (pl.BN == 32) PU_WG_DMA(32, 128, 1, 4);
+            else if (pl.BN == 32 && fq) hipLaunchKernelGGL((wgrad_dma_kernel<32, 128, 1, 4, 3, true, 4, true>), grid, dim3(256), 0, s, p);   // planned under math 1 only
+            else if (pl.BN == 32) hipLaunchKernelGGL((wgrad_dma_kernel<32, 128, 1, 4, 3, true>), grid, dim3(256), 0, s, p);
             else if (pl.BK == 192) PU_WG_DMA(64, 192, 2, 2);
             else if (pl.BK == 256 && fq) hipLaunchKernelGGL((wgrad_dma_kernel<128, 256, 2, 2, 3, true, 4, true>), grid, dim3(256), 0, s, p);
             else if (pl.BK == 256) hipLaunchKernelGGL((wgrad_dma_kernel<128, 256, 2, 2, 3, true>), grid, dim3(256), 0, s, p);
             else PU_WG_DMA(128, 128, 2, 2);
-        } else if (pl.qvec) {
-            if (pl.BK == 64) PU_WG_REG(64, 64, 2, 2, true);
-            else if (pl.BK == 256) PU_WG_REG(64, 256, 1, 4, true);
-            else PU_WG_REG(128, 128, 2, 2, true);
-        } else {
-            if (pl.BK == 64) PU_WG_REG(64, 64, 2, 2, false);
-            else if (pl.BK == 256) PU_WG_REG(64, 256, 1, 4, false);
-            else PU_WG_REG(128, 128, 2, 2, false);
+        } else {                              // pl.dma == pl.qvec: the register-staged kernel is the scalar loader's
+            if (pl.BK == 64) PU_WG_REG(64, 64, 2, 2);
+            else if (pl.BK == 256) PU_WG_REG(64, 256, 1, 4);
+            else PU_WG_REG(128, 128, 2, 2);
         }
 #undef PU_WG_DMA
 #undef PU_WG_REG

@@ -41,34 +41,36 @@ def assert_close(got, ref, rtol=1e-4, atol_rel=1e-5):
 
 
 CONV_CASES = [
-    # B, H, W, c0, c1, cout
+    # B, H, W, c0, c1, cout.  "wgrad:" names the weight-gradient kernel pu_wgrad_tile reports for the row
+    # today (math 1); the halo, math-0 and scalar weight-gradient kernels, which no row here reaches, and
+    # every other launch branch are covered by tests/wgrad_matrix.py
     (2, 16, 16, 1, 0, 8),       # single-channel stem kernel (N = 8)
     (2, 37, 70, 1, 0, 16),      # single-channel stem kernel (N = 16): partial 16 x 64 tiles
     (2, 40, 70, 1, 0, 64),      # single-channel stem kernel (N = 64): partial 16 x 64 tiles
     (1, 17, 33, 1, 0, 32),      # single-channel stem kernel (N = 32), odd sizes
-    (2, 12, 20, 8, 0, 16),      # vec4 loader, non-square
-    (3, 16, 16, 64, 0, 64),     # chunk16 loader, 256x64 tile
-    (2, 8, 8, 16, 16, 24),      # two sources (concat), N not a tile multiple
-    (1, 8, 8, 8, 8, 8),         # two sources, vec4
-    (2, 32, 32, 32, 0, 128),    # 128x128 tile
-    (1, 4, 4, 64, 64, 40),      # tiny M, 64x64 tile, split-K (fwd + dgrad with the n0 split)
-    (2, 8, 8, 48, 0, 64),       # wgrad 64x128 tile, ragged last k-tile, bias column sums
-    (1, 8, 8, 64, 64, 32),      # wgrad 64x128 tile, two sources
-    (2, 9, 13, 64, 64, 64),     # wgrad 64x576 6-wave tile (K = 2 x 576), two sources, ragged pixels
-    (2, 12, 20, 128, 128, 256), # wgrad split-once planes kernel (128x256): two sources, non-square
-    (1, 9, 13, 64, 0, 136),     # planes kernel: N not a tile multiple, ragged pixels, ragged k-tile
-    (2, 16, 32, 64, 64, 128),   # halo-reuse wgrad: two sources, 2 x 2 channel tiles, image-row edges
-    (1, 32, 16, 192, 0, 64),    # halo-reuse wgrad: 3 input-channel tiles, 16-wide rows (every stage at both edges)
-    (8, 64, 64, 64, 0, 64),     # halo wgrad (64-channel tile): 8 stages per split, the 3-deep raw ring wraps
-    (2, 32, 32, 128, 128, 128), # halo wgrad (128-channel tile): two sources, 2 input tiles
-    (1, 16, 48, 64, 128, 192),  # halo wgrad (64-channel tiles): 3 input x 3 output tiles, 3 stages per row
+    (2, 12, 20, 8, 0, 16),      # vec4 loader, non-square; wgrad: small-channel direct kernel (C = 8, N = 16)
+    (3, 16, 16, 64, 0, 64),     # chunk16 loader, 256x64 tile; wgrad: Winograd-domain kernel, 12 splits
+    (2, 8, 8, 16, 16, 24),      # two sources (concat), N not a tile multiple; wgrad: 32x128 x6 tile
+    (1, 8, 8, 8, 8, 8),         # two sources, vec4; wgrad: small-channel direct kernel (C = 16 through 8 + 8)
+    (2, 32, 32, 32, 0, 128),    # 128x128 tile; wgrad: 128x128 x6 tile, 8 splits
+    (1, 4, 4, 64, 64, 40),      # tiny M, 64x64 tile, split-K (fwd + dgrad with the n0 split); wgrad: 64x128 x6 tile
+    (2, 8, 8, 48, 0, 64),       # wgrad 64x128 x6 tile, ragged last k-tile, bias column sums
+    (1, 8, 8, 64, 64, 32),      # wgrad 32x128 x6 tile, two sources
+    (2, 9, 13, 64, 64, 64),     # wgrad 64x128 x6 tile (K = 1152: 9 k-tiles), two sources, ragged pixels
+    (2, 12, 20, 128, 128, 256), # wgrad Winograd-domain kernel (64x64 blocks, 8 splits): two sources, non-square
+    (1, 9, 13, 64, 0, 136),     # wgrad 128x128 x6 tile: N not a tile multiple, ragged pixels, ragged k-tile
+    (2, 16, 32, 64, 64, 128),   # wgrad Winograd-domain kernel: two sources, 2 x 2 channel blocks, image-row edges
+    (1, 32, 16, 192, 0, 64),    # wgrad Winograd-domain kernel: 3 input-channel blocks, 16-wide rows
+    (8, 64, 64, 64, 0, 64),     # wgrad Winograd-domain kernel: 256 splits of 2 stages
+    (2, 32, 32, 128, 128, 128), # wgrad Winograd column kernel (128x384, 128 pages): two sources, 2 input blocks
+    (1, 16, 48, 64, 128, 192),  # wgrad Winograd-domain kernel: 3 input x 3 output blocks, 12 splits
     (2, 37, 45, 16, 0, 16),     # small-channel direct kernels: several 16x32 tiles, ragged edges
     (1, 19, 70, 4, 4, 4),       # small-channel, two 4-channel sources, N = 4
     (1, 20, 36, 8, 4, 8),       # small-channel wgrad C = 12 (padded item groups), N = 8
     (2, 16, 40, 4, 0, 16),      # small-channel wgrad C = 4, N = 16
-    (2, 32, 64, 32, 0, 32),     # 32-channel lean tile (128 x 32): fwd and dgrad, N = 32
-    (1, 16, 64, 32, 32, 32),    # 32-channel lean tile, two sources
-    (32, 64, 64, 32, 0, 32),    # 256 x 32 lean tile (>= 480 tiles), the C4 64^2 level
+    (2, 32, 64, 32, 0, 32),     # 32-channel lean tile (128 x 32): fwd and dgrad, N = 32; wgrad: 32x128 x6 tile
+    (1, 16, 64, 32, 32, 32),    # 32-channel lean tile, two sources; wgrad: 32x128 x6 tile
+    (32, 64, 64, 32, 0, 32),    # 256 x 32 lean tile (>= 480 tiles), the C4 64^2 level; wgrad: 32x128 x6 tile, 328 splits
 ]
 
 # 8/16-channel layers on the 16x16x32 MFMA kernel (csrc/smallconv.hip; K.set_smallx6)

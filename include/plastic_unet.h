@@ -346,6 +346,8 @@ int pu_convert_bf16_f32(const void* x, float* y, long long n, void* stream);
 int pu_maxpool2_fwd_bf16(const void* x, void* y, int batch, int h, int w, int c, void* stream);
 int pu_maxpool2_bwd_bf16(const void* x, const void* dy, void* dx, int batch, int h, int w, int c,
                          int relu_mask, int accumulate, void* stream);
+/* x and dx (bf16, read and written four channels at a time) must be 8-byte aligned and w 16-byte
+ * aligned: anything else is PU_ERR_INVALID */
 int pu_outconv_fwd_bf16(const void* x, const float* w, const float* b, float* y, long long rows, int c,
                         void* stream);
 int pu_outconv_bwd_bf16(const void* x, const float* w, const float* dy, void* dx, float* dw, float* db,

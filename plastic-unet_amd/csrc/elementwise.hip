@@ -1071,6 +1071,8 @@ extern "C" int pu_maxpool2_bwd_bf16(const void* x, const void* dy, void* dx, int
 extern "C" int pu_outconv_fwd_bf16(const void* x, const float* w, const float* b, float* y, long long rows, int c,
                                    void* stream) {
     PU_REQUIRE(x && w && y && rows > 0 && c > 0 && c % 4 == 0, "pu_outconv_fwd_bf16: bad args");
+    PU_REQUIRE(((uintptr_t)x & 7) == 0 && ((uintptr_t)w & 15) == 0,
+               "pu_outconv_fwd_bf16: x must be 8-byte and w 16-byte aligned");
     const long long groups = (rows + 15) / 16;
     hipLaunchKernelGGL(outconv_fwd_kernel<__bf16>, dim3(grid_for(groups, 1, 8192)), dim3(256), 0, as_stream(stream),
                        (const __bf16*)x, w, b, y, rows, c);
@@ -1080,6 +1082,8 @@ extern "C" int pu_outconv_fwd_bf16(const void* x, const float* w, const float* b
 extern "C" int pu_outconv_bwd_bf16(const void* x, const float* w, const float* dy, void* dx, float* dw, float* db,
                                    long long rows, int c, int relu_mask, void* workspace, size_t ws_bytes, void* stream) {
     PU_REQUIRE(x && w && dy && dx && dw && db && rows > 0 && c % 4 == 0, "pu_outconv_bwd_bf16: bad args");
+    PU_REQUIRE((((uintptr_t)x | (uintptr_t)dx) & 7) == 0 && ((uintptr_t)w & 15) == 0,
+               "pu_outconv_bwd_bf16: x and dx must be 8-byte and w 16-byte aligned");
     const size_t need = pu_outconv_workspace_bytes(rows, c);
     if (!workspace || ws_bytes < need) return fail(PU_ERR_WORKSPACE, "pu_outconv_bwd_bf16: workspace %zu < %zu", ws_bytes, need);
     launch_outconv_bwd<__bf16>((const __bf16*)x, w, dy, (__bf16*)dx, dw, db, (float*)workspace, rows, c, relu_mask,

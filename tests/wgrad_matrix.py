@@ -401,7 +401,7 @@ def pairs():
 
 def demangle(sym):
     """'wgrad_dma_kernel<64,128,2,2,3,1,4,1>' from the Itanium name of a pu:: kernel template over
-    ints, bools and float / double (None: not a pu:: function)"""
+    ints, bools and float / double / __bf16 ('b') (None: not a pu:: function)"""
     m = re.match(r"_ZN2pu(\d+)", sym)
     if not m:
         return None
@@ -411,9 +411,9 @@ def demangle(sym):
         return name
     args, rest = [], rest[1:]
     while not rest.startswith("E"):
-        m = re.match(r"L[ib](\d+)E|([df])", rest)
+        m = re.match(r"L[ib](\d+)E|([df])|DF16(b)", rest)
         assert m, sym
-        args.append(m.group(1) or m.group(2))
+        args.append(m.group(1) or m.group(2) or m.group(3))
         rest = rest[m.end():]
     return "%s<%s>" % (name, ",".join(args))
 

@@ -81,6 +81,13 @@ using namespace pu;
 extern "C" int pu_adam_multi(const pu_adam_tensor* tensors, int n_tensors, double beta1, double beta2, double eps,
                              double weight_decay, double step_size, double bc2_sqrt, void* stream) {
     PU_REQUIRE(n_tensors >= 0 && (n_tensors == 0 || tensors), "pu_adam_multi: bad tensor list");
+    // the whole list is checked before the first launch: a bad tensor past the first 32 must not
+    // leave the ones before it stepped
+    for (int k = 0; k < n_tensors; ++k) {
+        const pu_adam_tensor& t = tensors[k];
+        PU_REQUIRE(t.numel >= 0, "pu_adam_multi: tensor %d", k);
+        PU_REQUIRE(t.numel == 0 || (t.param && t.grad && t.exp_avg && t.exp_avg_sq), "pu_adam_multi: tensor %d", k);
+    }
     int i = 0;
     while (i < n_tensors) {
         AdamBatch b;
@@ -88,9 +95,7 @@ extern "C" int pu_adam_multi(const pu_adam_tensor* tensors, int n_tensors, doubl
         int blocks = 0;
         while (i < n_tensors && b.count < ADAM_MAX_T) {
             const pu_adam_tensor& t = tensors[i++];
-            PU_REQUIRE(t.numel >= 0, "pu_adam_multi: tensor %d", i - 1);
             if (t.numel == 0) continue;     // an empty tensor has no storage: its pointers are null (torch)
-            PU_REQUIRE(t.param && t.grad && t.exp_avg && t.exp_avg_sq, "pu_adam_multi: tensor %d", i - 1);
             b.p[b.count] = t.param; b.g[b.count] = t.grad; b.m[b.count] = t.exp_avg; b.v[b.count] = t.exp_avg_sq;
             b.n[b.count] = t.numel;
             b.block_start[b.count] = blocks;

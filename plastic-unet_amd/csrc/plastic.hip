@@ -1136,9 +1136,11 @@ extern "C" int pu_plastic_head_fwd(const pu_plastic_head_args* a, void* stream) 
         if (R == 32) PU_FH3(T_, L_, W_, 32);                                                                \
         else PU_FH3(T_, L_, W_, FH_R);                                                                      \
     } while (0)
+    // one column tile per wave means N <= 128, and 32-row blocks need N >= 256 (16 tiles or more,
+    // two per wave): <.., 1, 32> cannot be launched and is not instantiated
 #define PU_FH(T_, L_)                                                                                       \
     do {                                                                                                    \
-        if (tpw <= 1) PU_FH2(T_, L_, 1);                                                                    \
+        if (tpw <= 1) PU_FH3(T_, L_, 1, FH_R);                                                              \
         else if (tpw <= 2) PU_FH2(T_, L_, 2);                                                               \
         else PU_FH2(T_, L_, 4);                                                                             \
     } while (0)
@@ -1299,6 +1301,7 @@ extern "C" int pu_bce_fwd(const float* y, const float* t, long long n, float* lo
                           void* stream) {
     PU_REQUIRE(y && t && loss && n > 0, "pu_bce_fwd: bad args");
     if (!workspace || ws_bytes < pu_bce_workspace_bytes(n)) return fail(PU_ERR_WORKSPACE, "pu_bce_fwd: workspace");
+    PU_REQUIRE(((uintptr_t)workspace & 7) == 0, "pu_bce_fwd: workspace must be 8-byte aligned");   // fp64 partials
     int blocks = grid_for(n, 256, BCE_BLOCKS);
     hipLaunchKernelGGL(bce_partial_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), y, t, n, (double*)workspace);
     hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, as_stream(stream), (const double*)workspace, blocks, n,

@@ -449,7 +449,9 @@ def test_fused_head_trace_equals_two_launch_path(B, N, rule):
 def test_fused_head_equals_outconv_then_head(rule, B, N, C, dt):
     """pu_plastic_head_fwd (outconv + Weff GEMM on v_mfma_f32_16x16x4_f32 + sigmoid + trace update,
     one launch) is bit-identical to the two-kernel path outconv_fwd -> plastic_fwd: the outconv sum
-    uses the same lane tree, and the f32 MFMA is a k-ordered fma chain like the VALU head."""
+    uses the same lane tree, and the f32 MFMA is a k-ordered fma chain like the VALU head.
+    (tests/head_matrix.py now holds the launcher's branch list - every <T, L, TPW, R>, the pipe gate,
+    the LDS chunks - and test_head_matrix_gpu.py holds this identity on every one of its rows.)"""
     g = torch.Generator().manual_seed(N + C)
     feat = torch.randn(B, N, N, C, generator=g).relu_().to(dt).to(DEV)
     wo = (torch.randn(C, generator=g) * 0.2).to(DEV)

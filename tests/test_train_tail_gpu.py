@@ -78,7 +78,8 @@ def test_plastic_bwd_ragged_against_fp64(B, N, zero_h):
     """dX = G Weff^T, dw = sum_b X_b^T G_b, dalpha = sum_b (X_b^T G_b) . H_b, G = dY (1 - Y) Y in
     fp64, at N that is no multiple of the tile or of the k chunk: the range guards of the loaders
     decide and a partial last chunk goes through the register prefetch.  With H = 0 dalpha is
-    exactly 0."""
+    exactly 0.  (tests/head_matrix.py now holds the branch list of pu_plastic_bwd: these shapes in
+    every output form, with per-entry bounds.)"""
     (X, H, w, al, Y, dY), ref = _head_case(B, N, zero_h)
     dx, dw, da = K.plastic_bwd(X, H, w, al, Y, dY)
     for name, got, r in zip(("dx", "dw", "dalpha"), (dx, dw, da), ref):

@@ -207,9 +207,10 @@ typedef struct {
 } pu_wgrad_args;
 
 size_t pu_wgrad_workspace_bytes(const pu_wgrad_args* a);
-/* the tile (bn x bk), loader (qvec: 0 scalar, 1 float4, 2 small-channel direct kernel, 3 halo-reuse kernel,
- * 4 stem kernel, 5 Winograd-domain kernel, 6 pointwise small-channel kernel) and
- * pixel-row split count pu_wgrad would use */
+/* the tile (bn x bk), kernel (qvec: 0 register-staged GEMM tile with the scalar loader, 1 direct-to-LDS
+ * GEMM tile with the float4 loader, 2 small-channel direct kernel, 3 halo-reuse kernel, 4 stem kernel,
+ * 5 Winograd-domain kernel in its 64 x 64 or its column form (bn 64 or 128), 6 pointwise small-channel
+ * kernel) and split count (slab pages) pu_wgrad would use */
 int pu_wgrad_tile(const pu_wgrad_args* a, int* bn, int* bk, int* qvec, int* splits);
 int pu_wgrad(const pu_wgrad_args* a, void* workspace, size_t workspace_bytes, void* stream);
 /* pu_wgrad in two launches-worth of phases for per-kernel timing: phase 1 = the split-K GEMM

@@ -17,11 +17,6 @@
 #ifndef PU_NO_ILV
 #define PU_NO_ILV 0   // 1: leave MFMA / VALU placement to the scheduler (A/B builds)
 #endif
-// wgrad_wino_x6_kernel ablations (timing only, wrong results): 1 no MFMAs, 2 no plane formation
-// (VALU + LDS stores), 3 no global loads, 4 no per-sub-stage barrier
-#ifndef PU_WW_ABL
-#define PU_WW_ABL 0
-#endif
 
 namespace pu {
 
@@ -898,11 +893,6 @@ __global__ __launch_bounds__(512) void wgrad_wino_x6_kernel(const WinoWgradParam
     };
     wg_f32x2 d[4][4], e[2][2];
     auto load_x = [&](int r) {
-        if (PU_WW_ABL == 3) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) d[r][s] = wg_f32x2{1.f + r, 2.f - s};
-            return;
-        }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             unsigned vo = xv[r];
@@ -913,10 +903,6 @@ __global__ __launch_bounds__(512) void wgrad_wino_x6_kernel(const WinoWgradParam
         }
     };
     auto load_g = [&](int a) {
-        if (PU_WW_ABL == 3) {
-            e[a][0] = e[a][1] = wg_f32x2{0.5f, 0.25f * a};
-            return;
-        }
 #pragma unroll
         for (int s = 0; s < 2; ++s)
             e[a][s] = __builtin_bit_cast(wg_f32x2, __builtin_amdgcn_raw_buffer_load_b64(
@@ -926,7 +912,6 @@ __global__ __launch_bounds__(512) void wgrad_wino_x6_kernel(const WinoWgradParam
     // sub-stage slots sx / sg: image (j, plane) at (3 j + plane) * WW_IMG
     auto form = [&](auto i_c, char* sx, char* sg) {
         constexpr int i = decltype(i_c)::value;
-        if (PU_WW_ABL == 2) return;
         wg_f32x2 t[4], u[2];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -984,12 +969,6 @@ __global__ __launch_bounds__(512) void wgrad_wino_x6_kernel(const WinoWgradParam
         const char* gb = sg + ga + jj * 3 * WW_IMG;
         const wg_bf16x8 qh = tr2(xb), qm = tr2(xb + WW_IMG), ql = tr2(xb + 2 * WW_IMG);
         const wg_bf16x8 ph = tr2(gb), pm = tr2(gb + WW_IMG), pl = tr2(gb + 2 * WW_IMG);
-        if (PU_WW_ABL == 1) {             // keep the operand reads alive, drop the MFMAs
-            acc[x][0] += __builtin_bit_cast(float, __builtin_shufflevector(qh, qm, 0, 1)) +
-                         __builtin_bit_cast(float, __builtin_shufflevector(ql, ph, 0, 1)) +
-                         __builtin_bit_cast(float, __builtin_shufflevector(pm, pl, 0, 1));
-            return;
-        }
         f32x16 c = acc[x];
         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qm, pm, c, 0, 0, 0);   // small terms first
         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ql, ph, c, 0, 0, 0);
@@ -1033,7 +1012,7 @@ __global__ __launch_bounds__(512) void wgrad_wino_x6_kernel(const WinoWgradParam
         // Interleave: the wave's 12 MFMAs spread over the forming work (~110 VALU + 24 LDS
         // stores) instead of 6 before and 6 after it - the two waves of a SIMD run the same phase
         // between barriers, so MFMAs bunched at the ends leave the matrix pipe idle during the VALU
-#if !PU_NO_ILV && PU_WW_ABL == 0
+#if !PU_NO_ILV
         __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);       // position 0 operands
 #pragma unroll
         for (int q = 0; q < 12; ++q) {
@@ -1043,11 +1022,9 @@ __global__ __launch_bounds__(512) void wgrad_wino_x6_kernel(const WinoWgradParam
             if (q == 2) __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);   // position 1 operands
         }
 #endif
-        if (PU_WW_ABL != 4) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");     // s_barrier is no compiler fence: keep LDS reads behind it
-        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");     // s_barrier is no compiler fence: keep LDS reads behind it
     };
 
     // prologue: stage 0 whole, sub-stage (0, 0) formed, stage 1's row 0 in flight
@@ -1645,9 +1622,6 @@ __global__ __launch_bounds__(256) void wgrad_pw_kernel(const WgradParams p) {
 // block's partial goes to slab row [block][n][tap*C + c] (bias at column K) and the fixed-order
 // fp64 split reduction below finishes it - deterministic like the GEMM path.
 constexpr int SW_TH = 16, SW_TW = 32;
-#ifndef PU_SW_ROW
-#define PU_SW_ROW 1     // 1: an item is a row of 3 taps over 4-pixel quads; 0: one tap per pixel
-#endif
 
 // 4x4 outer-product accumulate of 4 output channels g (x) 4 input channels x: channel pairs on
 // v_pk_fma_f32 (one rounding per element, as fmaf)
@@ -1665,10 +1639,10 @@ template <int C, int N>
 __global__ __launch_bounds__(256) void wgrad_small_kernel(const WgradParams p) {
     constexpr int HH = SW_TH + 2, HWD = SW_TW + 2;
     constexpr int CP = (C + 3) & ~3, C4 = CP / 4, N4 = N / 4;
-    // weight items: (tap row r, 4 output x 4 input channels) with the 3 taps of the row, or
-    // (tap, 4 x 4) - plus bias items (4 output channels)
-    constexpr int RT = PU_SW_ROW ? 3 : 1;                 // taps per item
-    constexpr int WITEMS = (9 / RT) * N4 * C4;
+    // weight items: (tap row r, 4 output x 4 input channels) with the 3 taps of the row, plus
+    // bias items (4 output channels)
+    constexpr int RT = 3;                                 // taps per item
+    constexpr int WITEMS = 3 * N4 * C4;
     constexpr int ITEMS = WITEMS + N4;
     // LDS bank conflicts (64 banks: a ds_read_b128 serves 16 lanes per cycle): a group's items
     // padded to a multiple of 16 lanes keeps each 16-lane phase inside one pixel group, and a
@@ -1689,16 +1663,15 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const WgradParams p) {
     const int item = tid % ITEMS_P, grp = tid / ITEMS_P;
     const bool active = grp < GROUPS && item < ITEMS;
     const bool wi = item < WITEMS;
-    int tq = 0, co4 = 0, ci4 = 0;                          // tq: tap row (RT = 3) or tap
+    int tr = 0, co4 = 0, ci4 = 0;                          // tr: tap row
     if (wi) {
-        tq = item / (N4 * C4);
-        const int rem = item - tq * (N4 * C4);
+        tr = item / (N4 * C4);
+        const int rem = item - tr * (N4 * C4);
         co4 = rem / C4;
         ci4 = rem - co4 * C4;
     } else {
         co4 = item - WITEMS;
     }
-    const int tr = RT == 3 ? tq : tq / 3, ts = RT == 3 ? 0 : tq - tr * 3;
     wg_f32x2 acc[RT][4][2];
 #pragma unroll
     for (int t = 0; t < RT; ++t)
@@ -1771,45 +1744,30 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const WgradParams p) {
         if (t + (int)gridDim.x < ntiles) load_tile(t + gridDim.x);
         __syncthreads();
         if (active) {
-            if (RT == 3) {
-                // 4 consecutive output pixels x the row's 3 taps: 4 gradient + 6 halo reads per
-                // 192 fmas (the per-tap form: 2 reads per 16)
-                constexpr int QW = SW_TW / 4;
-                for (int pq = grp; pq < SW_TH * QW; pq += GROUPS) {
-                    const int row = pq / QW, col0 = (pq - row * QW) * 4;
-                    f32x4 g[4];
+            // 4 consecutive output pixels x the row's 3 taps: 4 gradient + 6 halo reads per
+            // 192 fmas (the per-tap form: 2 reads per 16)
+            constexpr int QW = SW_TW / 4;
+            for (int pq = grp; pq < SW_TH * QW; pq += GROUPS) {
+                const int row = pq / QW, col0 = (pq - row * QW) * 4;
+                f32x4 g[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    g[u] = *reinterpret_cast<const f32x4*>(gt + (row * SW_TW + col0 + u) * N + 4 * co4);
+                if (wi) {
+                    f32x4 x[6];
+#pragma unroll
+                    for (int v = 0; v < 6; ++v)
+                        x[v] = *reinterpret_cast<const f32x4*>(halo + ((row + tr) * HWP + col0 + v) * CP + 4 * ci4);
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
-                        g[u] = *reinterpret_cast<const f32x4*>(gt + (row * SW_TW + col0 + u) * N + 4 * co4);
-                    if (wi) {
-                        f32x4 x[6];
 #pragma unroll
-                        for (int v = 0; v < 6; ++v)
-                            x[v] = *reinterpret_cast<const f32x4*>(halo + ((row + tr) * HWP + col0 + v) * CP + 4 * ci4);
+                        for (int s3 = 0; s3 < RT; ++s3) sw_fma44(acc[s3], g[u], x[u + s3]);
+                } else {
 #pragma unroll
-                        for (int u = 0; u < 4; ++u)
-#pragma unroll
-                            for (int s3 = 0; s3 < RT; ++s3) sw_fma44(acc[s3], g[u], x[u + s3]);
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            acc[0][0][0] += wg_f32x2{g[u][0], g[u][1]};
-                            acc[0][0][1] += wg_f32x2{g[u][2], g[u][3]};
-                        }
+                    for (int u = 0; u < 4; ++u) {
+                        acc[0][0][0] += wg_f32x2{g[u][0], g[u][1]};
+                        acc[0][0][1] += wg_f32x2{g[u][2], g[u][3]};
                     }
-                }
-            } else if (wi) {
-                for (int pp = grp; pp < SW_TH * SW_TW; pp += GROUPS) {
-                    const int row = pp / SW_TW, col = pp - row * SW_TW;
-                    const f32x4 g4 = *reinterpret_cast<const f32x4*>(gt + pp * N + 4 * co4);
-                    const f32x4 x4 = *reinterpret_cast<const f32x4*>(halo + ((row + tr) * HWP + col + ts) * CP + 4 * ci4);
-                    sw_fma44(acc[0], g4, x4);
-                }
-            } else {
-                for (int pp = grp; pp < SW_TH * SW_TW; pp += GROUPS) {
-                    const f32x4 g4 = *reinterpret_cast<const f32x4*>(gt + pp * N + 4 * co4);
-                    acc[0][0][0] += wg_f32x2{g4[0], g4[1]};
-                    acc[0][0][1] += wg_f32x2{g4[2], g4[3]};
                 }
             }
         }
@@ -1839,7 +1797,7 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const WgradParams p) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) v[e] += smem[(g * ITEMS + tid) * ACC + t * 16 + e];
             if (tid < WITEMS) {
-                const int tap = RT == 3 ? 3 * tr + t : tq;
+                const int tap = 3 * tr + t;
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -2134,249 +2092,6 @@ __global__ __launch_bounds__(384) void wgrad_finish_cols_kernel(const float* __r
     } else {
         for (int i = threadIdx.x; i < run; i += blockDim.x) o[i] = accumulate ? o[i] + tr[i] : tr[i];
     }
-}
-
-struct WgradPlan {
-    int BN, BK, splits, mps, Nr, Kc, Kcp, M, K, C, G, gx, gy;
-    bool qvec, dma, small, halo, stem;
-    bool wino = false;                        // Winograd-domain kernel (wgrad_wino_x6_kernel)
-    bool cols = false;                        // ... its one-column-per-block form (wgrad_wino_cols_x6_kernel)
-    int Gfin = 1;                             // ... the 64 x 64 plan's reduction groups, which its finisher follows
-    bool pw = false;                          // pointwise small-channel kernel (wgrad_pw_kernel)
-    int tiles = 0, tps = 0;
-    int nt = 1;                               // halo kernel: 64-channel output tiles per block
-    int tiles_w, tiles_h;
-    size_t slab_bytes() const { return (size_t)splits * Nr * Kcp * sizeof(float); }
-    size_t part_bytes() const { return G > 1 ? (size_t)G * Nr * Kcp * sizeof(double) : 0; }
-    size_t ws_bytes() const { return ((slab_bytes() + 255) / 256) * 256 + part_bytes(); }
-};
-
-static bool stem_wgrad_ok(const pu_wgrad_args* a) {
-    return a->c0 == 1 && a->c1 == 0 && (a->n == 8 || a->n == 16 || a->n == 32 || a->n == 64) && a->kh == 3 && a->kw == 3 && a->stride == 1 &&
-           a->pad == 1 && a->in_h == a->out_h && a->in_w == a->out_w && a->bias_mode == 1 &&
-           ((uintptr_t)a->rows & 15) == 0;
-}
-
-// 1x1 / s1 / p0 same-size conv, one source, (C, N) an instantiated wgrad_pw_kernel pair
-static bool pw_wgrad_ok(const pu_wgrad_args* a) {
-    const int C = a->c0, N = a->n;
-    return a->c1 == 0 && a->kh == 1 && a->kw == 1 && a->stride == 1 && a->pad == 0 && a->in_h == a->out_h &&
-           a->in_w == a->out_w && a->bias_mode != 2 && (C == 3 || C == 4) && (N == 4 || N == 8 || N == 16) &&
-           (((uintptr_t)a->rows & 15) == 0) && (C % 4 || ((uintptr_t)a->src0 & 15) == 0);
-}
-
-static bool small_wgrad_ok(const pu_wgrad_args* a) {
-    const int C = a->c0 + a->c1;
-    return (C == 1 || C == 4 || C == 8 || C == 12 || C == 16) &&
-           (a->n == 4 || a->n == 8 || a->n == 16) && a->kh == 3 && a->kw == 3 && a->stride == 1 && a->pad == 1 &&
-           a->in_h == a->out_h && a->in_w == a->out_w && a->bias_mode != 2 &&
-           (C == 1 || (a->c0 % 4 == 0 && a->c1 % 4 == 0));
-}
-
-// reduction groups: one pass (G = 1, each thread sums every split of its entry) when the slab
-// has enough entries to fill the chip; otherwise G groups of >= 8 splits each, then G partials
-static void plan_groups(WgradPlan* pl) {
-    const long long total = (long long)pl->Nr * pl->Kcp;
-    int G = (int)ceil_div(262144LL, total);
-    const int by_len = ceil_div(pl->splits, 8);
-    if (G > by_len) G = by_len;
-    if (G > 16) G = 16;
-    pl->G = G < 1 ? 1 : G;
-}
-
-// the GEMM's dimensions and the slab's shape, fp32 and bf16 alike: M pixel rows, K = taps x C,
-// Nr x Kc slab entries with the bias as row N (mode 2) or column K (mode 1).  Kcp, the slab's row
-// stride, is Kc rounded up to 4 floats: phase 2 reads and sums every slab as 16-byte quads.
-static int plan_dims(const pu_wgrad_args* a, WgradPlan* pl, const char* who) {
-    const long long M = (long long)a->batch * a->out_h * a->out_w;
-    PU_REQUIRE(M < (1LL << 31), "%s: too many pixels", who);
-    pl->M = (int)M;
-    pl->C = a->c0 + a->c1;
-    pl->K = a->kh * a->kw * pl->C;
-    pl->Nr = a->n + (a->bias_mode == 2 ? 1 : 0);
-    pl->Kc = pl->K + (a->bias_mode == 1 ? 1 : 0);
-    pl->Kcp = (pl->Kc + 3) / 4 * 4;
-    return PU_OK;
-}
-
-// the halo kernels (wgrad_halo_x6_kernel, wgrad_halo_bf16_kernel): 64 NT x 64 x 9-tap tiles,
-// 16-pixel stages split so that one round of blocks fills the chip
-static void plan_halo(const pu_wgrad_args* a, WgradPlan* pl) {
-    pl->halo = true;
-    pl->nt = a->n % 128 == 0 ? 2 : 1;    // 128 output channels per block when they divide
-    pl->BN = 64 * pl->nt;
-    pl->BK = 9 * 64;
-    pl->gx = pl->C / 64;
-    pl->gy = a->n / pl->BN;
-    int splits = (pl->nt == 2 ? 256 : 512) / (pl->gx * pl->gy);   // one 8-wave / two 4-wave blocks per CU
-    const int stages = pl->M / 16;
-    if (splits > stages) splits = stages;
-    if (splits < 1) splits = 1;
-    pl->mps = ceil_div(stages, splits) * 16;
-    pl->splits = ceil_div(pl->M, pl->mps);
-    plan_groups(pl);
-}
-
-// the Winograd-domain kernel: 3x3 / s1 / p1 on an even same-size grid, 64-channel input blocks
-// from one source each, 64-channel output blocks, the 6-product arithmetic, byte offsets of the
-// (shifted) sources and of dZ under 2^31; PU_WINO_WGRAD=0 keeps the direct kernels (A/B runs)
-// Fewest tiles at which the column plan (wgrad_wino_cols_x6_kernel) is taken: C2's smallest qualifying
-// layers (the 8 x 8 level at batch 32) have 512; the measured gate is in DESIGN.md section 2.
-constexpr int WWR_MIN_TILES = 512;
-
-static bool wino_wgrad_ok(const pu_wgrad_args* a, const WgradPlan* pl) {
-    static const bool on = [] {
-        const char* e = getenv("PU_WINO_WGRAD");
-        return !(e && e[0] == '0');
-    }();
-    if (!on || a->math != 1 || !pl->qvec) return false;
-    if (a->kh != 3 || a->kw != 3 || a->stride != 1 || a->pad != 1) return false;
-    if (a->in_h != a->out_h || a->in_w != a->out_w || (a->out_h & 1) || (a->out_w & 1)) return false;
-    if (a->c0 % 64 || a->c1 % 64 || a->n % 64 || a->bias_mode == 2) return false;
-    const long long px = (long long)a->batch * a->in_h * a->in_w + a->in_w + 1;
-    if (px * (a->c0 > a->c1 ? a->c0 : a->c1) * 4 >= (1LL << 31)) return false;
-    if ((long long)a->batch * a->out_h * a->out_w * a->n * 4 >= (1LL << 31)) return false;
-    return (((uintptr_t)a->rows | (uintptr_t)a->src0 | (uintptr_t)a->src1) & 7) == 0;
-}
-
-// Measured alternatives: capping the GEMM-path split count at 2 / 4 (round 3: C2 4060 -> 2262 /
-// 2968 img/s - the deep layers' slab traffic is cheaper than idle CUs); round 1: 64 x 576 6-wave tiles for the 64-channel layers (-6 %), a
-// 3-wave 64 x 192 tile (-8 %), a split-once-planes kernel that still staged fp32 through LDS
-// (-10...-25 %); the halo kernel below replaced all of them on 3x3/s1 layers.
-static int plan_wgrad(const pu_wgrad_args* a, WgradPlan* pl) {
-    PU_REQUIRE(a && a->batch > 0 && a->out_h > 0 && a->out_w > 0 && a->in_h > 0 && a->in_w > 0, "pu_wgrad: bad grid");
-    PU_REQUIRE(a->kh > 0 && a->kw > 0 && a->stride > 0 && a->pad >= 0, "pu_wgrad: bad taps");
-    PU_REQUIRE(a->rows && a->n > 0 && a->src0 && a->c0 > 0 && (a->c1 == 0 || a->src1), "pu_wgrad: operands");
-    PU_REQUIRE(a->n % 4 == 0, "pu_wgrad: n (%d) must be a multiple of 4", a->n);
-    PU_REQUIRE(a->bias_mode >= 0 && a->bias_mode <= 2, "pu_wgrad: bias_mode");
-    PU_REQUIRE(a->bias_mode == 0 || a->dbias, "pu_wgrad: dbias missing");
-    PU_REQUIRE(a->dweight, "pu_wgrad: dweight missing");
-    PU_REQUIRE(a->math >= 0 && a->math <= 2, "pu_wgrad: math %d", a->math);
-    PU_REQUIRE(a->math != 2 || stem_wgrad_ok(a), "pu_wgrad: math 2 (bf16 rows) is the single-channel stem only");
-    if (int st = plan_dims(a, pl, "pu_wgrad")) return st;
-    const long long M = pl->M;
-    pl->qvec = (a->c0 % 4 == 0) && (a->c1 % 4 == 0);
-    pl->small = small_wgrad_ok(a);
-    pl->stem = stem_wgrad_ok(a);
-    pl->pw = pw_wgrad_ok(a);
-    pl->halo = false;
-    if (pl->qvec) {
-        PU_REQUIRE(((uintptr_t)a->src0 & 15) == 0 && ((uintptr_t)a->src1 & 15) == 0, "pu_wgrad: sources must be 16-byte aligned");
-    }
-    PU_REQUIRE(((uintptr_t)a->rows & 15) == 0, "pu_wgrad: rows must be 16-byte aligned");
-    pl->dma = pl->qvec;
-    if (pl->pw) {                      // pointwise: contiguous pixel ranges, one slab row block each
-        pl->splits = (int)(M / 256 < 1024 ? (M + 255) / 256 : 1024);
-        pl->mps = (int)ceil_div(M, (long long)pl->splits);
-        pl->splits = (int)ceil_div(M, (long long)pl->mps);
-        pl->BN = a->n; pl->BK = pl->K; pl->gx = pl->gy = 1; pl->dma = false;
-        pl->tiles_w = pl->tiles_h = 0;
-        plan_groups(pl);
-        return PU_OK;
-    }
-    if (pl->small || pl->stem) {       // direct kernels: one slab row block per block
-        pl->tiles_w = ceil_div(a->out_w, pl->stem ? SWS_TW : SW_TW);
-        pl->tiles_h = ceil_div(a->out_h, pl->stem ? SWS_TH : SW_TH);
-        const long long ntiles = (long long)a->batch * pl->tiles_w * pl->tiles_h;
-        pl->splits = (int)(ntiles < 1024 ? ntiles : 1024);
-        pl->BN = a->n; pl->BK = pl->K; pl->gx = pl->gy = 1; pl->mps = 0; pl->dma = false;
-        plan_groups(pl);
-        return PU_OK;
-    }
-    // the direct-to-LDS kernel tiles only the N x K GEMM (bias via LDS column sums); the
-    // register-staged kernel carries the bias as an extra ones column / row
-    const int ext_n = pl->dma ? a->n : pl->Nr;
-    const int ext_k = pl->dma ? pl->K : pl->Kc;
-    int occ;  // resident blocks per CU (LDS / VGPR limited, from the resource-usage report)
-    if (ext_k <= 64) { pl->BN = 64; pl->BK = 64; occ = pl->dma ? 6 : 7; }
-    else if (ext_n <= 64 && !pl->dma) { pl->BN = 64; pl->BK = 256; occ = 3; }
-    else if (ext_n <= 32 && a->math == 1) { pl->BN = 32; pl->BK = 128; occ = 4; }   // 32-channel layers (C4/C5)
-    else if (ext_n <= 64) {
-        // BK 128 (4 resident blocks) unless 192 (3 resident) pads k less - e.g. K = 9 taps x 64
-        const bool b192 = ceil_div(ext_k, 192) * 192 < ceil_div(ext_k, 128) * 128;
-        pl->BN = 64; pl->BK = b192 ? 192 : 128; occ = b192 ? 3 : 4;
-    }
-    else { pl->BN = 128; pl->BK = 128; occ = pl->dma ? 3 : 4; }
-    // 6-product path: a 128 x 256 tile (2x2 waves of 64 x 128) splits 6 operand fragments per 48
-    // MFMAs instead of 4 per 24, when K pads no worse than with 128
-    if (a->math == 1 && pl->dma && pl->BN == 128 &&
-        ceil_div(ext_k, 256) * 256 <= ceil_div(ext_k, 128) * 128) {
-        pl->BK = 256;
-        occ = 2;
-    }
-    pl->halo = false;
-    if (wino_wgrad_ok(a, pl) && a->c0 % 128 == 0 && a->c1 % 128 == 0 && a->n % 128 == 0 &&
-        a->batch * (a->out_h / 2) * (a->out_w / 2) >= WWR_MIN_TILES) {
-        // column plan: (C / 128) x (N / 128) channel blocks x 4 position columns x the 64 x 64 plan's
-        // tile splits, one 512-thread block per CU.  The slab has 4 pages per tile split (virtual split 4 z + j)
-        // of [Nr][3 C (+ 1 bias column)] entries: splits, Kc and Kcp describe those pages.
-        pl->wino = pl->cols = true;
-        pl->BN = 128;
-        pl->BK = 3 * 128;
-        pl->gx = pl->C / 128;
-        pl->gy = a->n / 128;
-        pl->tiles = a->batch * (a->out_h / 2) * (a->out_w / 2);
-        const int stages = ceil_div(pl->tiles, 16);
-        int zs = 256 / (4 * pl->gx * pl->gy);
-        if (zs > stages) zs = stages;
-        if (zs < 1) zs = 1;
-        pl->tps = ceil_div(stages, zs) * 16;
-        pl->splits = 4 * ceil_div(pl->tiles, pl->tps);
-        pl->mps = pl->tps * 4;
-        pl->Kc = 3 * pl->C + (a->bias_mode == 1 ? 1 : 0);
-        pl->Kcp = (pl->Kc + 3) / 4 * 4;
-        // the finisher sums the splits in the groups the 64 x 64 plan of this call would use
-        // (C, N >= 128: one or two)
-        {
-            WgradPlan q = *pl;
-            q.splits = pl->splits / 4;
-            q.Kcp = (9 * pl->C + (a->bias_mode == 1 ? 1 : 0) + 3) / 4 * 4;
-            plan_groups(&q);
-            pl->Gfin = q.G;
-        }
-        pl->G = 1;                           // no fp64 partials in the workspace
-        return PU_OK;
-    }
-    if (wino_wgrad_ok(a, pl)) {
-        // one 512-thread block per CU: (C / 64) x (N / 64) channel blocks x tile splits of whole
-        // 16-tile stages
-        pl->wino = true;
-        pl->BN = 64;
-        pl->BK = 9 * 64;
-        pl->gx = pl->C / 64;
-        pl->gy = a->n / 64;
-        pl->tiles = a->batch * (a->out_h / 2) * (a->out_w / 2);
-        const int stages = ceil_div(pl->tiles, 16);
-        int splits = 256 / (pl->gx * pl->gy);
-        if (splits > stages) splits = stages;
-        if (splits < 1) splits = 1;
-        pl->tps = ceil_div(stages, splits) * 16;
-        pl->splits = ceil_div(pl->tiles, pl->tps);
-        pl->mps = pl->tps * 4;
-        plan_groups(pl);
-        return PU_OK;
-    }
-    if (a->math == 1 && pl->dma && a->kh == 3 && a->kw == 3 && a->stride == 1 && a->pad == 1 &&
-        a->in_h == a->out_h && a->in_w == a->out_w && a->out_w % 16 == 0 && a->c0 % 64 == 0 && a->c1 % 64 == 0 &&
-        a->n % 64 == 0 && a->bias_mode != 2 && (long long)a->batch * a->in_h * a->in_w * (pl->C) < (1LL << 31)) {
-        plan_halo(a, pl);
-        return PU_OK;
-    }
-    pl->gx = ceil_div(ext_k, pl->BK);
-    pl->gy = ceil_div(ext_n, pl->BN);
-    const int tiles = pl->gx * pl->gy;
-    // one full round of resident blocks: a grid a few blocks past a multiple of the resident
-    // slots costs a whole extra round
-    const int slots = 256 * occ;
-    int splits = slots / tiles;
-    int max_splits = ceil_div(M, 256);
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    int mps = ceil_div(ceil_div(M, splits), WG_BM) * WG_BM;
-    pl->mps = mps;
-    pl->splits = ceil_div(M, mps);
-    plan_groups(pl);
-    return PU_OK;
 }
 
 // ------------------------------------------------------------------ bf16 weight gradient (C3)
@@ -2801,24 +2516,249 @@ __global__ __launch_bounds__(256) void wgrad_reduce_wide_kernel(const float* __r
     store_oihw(n, k, (float)sum, K, C, kh, kw, bias_mode, dw, db, accumulate);
 }
 
-// the transposed (coalesced float4 stores) or the quad (scattered stores) finisher over `count`
-// partials: the fp32 slab's splits, or the fp64 partials of wgrad_sum_splits4_kernel
-template <typename T>
-static void launch_finisher(bool transposed, const T* part, int count, const WgradPlan& pl, const pu_wgrad_args* a,
-                            hipStream_t s) {
-    const int taps = a->kh * a->kw;
-    if (transposed) {
-        hipLaunchKernelGGL(wgrad_finish_t_kernel<T>, dim3((unsigned)ceil_div(pl.C, 256), (unsigned)a->n),
-                           dim3((unsigned)(64 * taps)), 0, s, part, count, pl.Nr, pl.Kcp, pl.K, pl.C, taps, a->bias_mode,
-                           a->dweight, a->dbias, a->accumulate);
-        return;
-    }
-    const long long threads = (long long)pl.Nr * pl.Kcp / 4 + (a->bias_mode == 2 ? pl.C : 0);
-    hipLaunchKernelGGL(wgrad_finish4_kernel<T>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, part, count,
-                       pl.Nr, pl.Kcp, a->n, pl.K, pl.C, a->kh, a->kw, a->bias_mode, a->dweight, a->dbias, a->accumulate);
+// ------------------------------------------------------------------ host: plan, launch, reduce
+// One plan per call, fp32 and bf16 entries alike: which phase-1 kernel runs (kind), how its grid
+// and slab are shaped, and which phase-2 reduction finishes it (reducer).
+enum WgradKind {
+    WK_STEM,        // wgrad_stem_kernel: the single-channel 3x3 stem, fp32 or bf16 rows
+    WK_PW,          // wgrad_pw_kernel: 1x1 on 3 or 4 input channels
+    WK_SMALL,       // wgrad_small_kernel: 3x3 on up to 16 x 16 channels
+    WK_WINO,        // wgrad_wino_x6_kernel: Winograd domain, 64 x 64 channel blocks
+    WK_WINO_COLS,   // wgrad_wino_cols_x6_kernel: 128 x 128 blocks, one position column each
+    WK_HALO,        // wgrad_halo_x6_kernel
+    WK_DMA,         // wgrad_dma_kernel: GEMM tile, float4 sources straight to LDS
+    WK_REG,         // wgrad_kernel: GEMM tile, register-staged scalar loader
+    WK_BF16,        // wgrad_bf16_kernel: 128 x 128 GEMM tile
+    WK_BF16_HALO,   // wgrad_halo_bf16_kernel
+};
+
+enum WgradReducer {
+    RD_COLS,        // wgrad_finish_cols_kernel: combines the column plan's pages
+    RD_WIDE,        // wgrad_reduce_wide_kernel: one launch
+    RD_SPLITS,      // a finisher over the fp32 splits
+    RD_GROUPS,      // wgrad_sum_splits4_kernel into G fp64 partials, then a finisher over those
+};
+
+struct WgradPlan {
+    WgradKind kind;
+    WgradReducer reducer;
+    bool fq = false;            // WK_DMA: the tile's FQ form
+    bool transposed = false;    // RD_SPLITS / RD_GROUPS: the transposed finisher, not the quad one
+    bool dw_vec = false;        // RD_COLS: float4 stores (dweight 16-byte aligned)
+    int M, K, C, Nr, Kc, Kcp;   // the GEMM and its [Nr][Kcp] result (plan_dims)
+    int BN, BK, gx, gy, splits, mps;
+    int G;                      // reduction groups whose fp64 partials lie in the workspace
+    // the slab is splits x pages pages of [Nr][pKcp] floats with the bias at column pK: one page
+    // of the whole result per split, but the column plan's 4 position columns write [Nr][3 C (+ 1)]
+    int pages, pK, pKc, pKcp;
+    int fin_groups = 1;         // RD_COLS: the groups its finisher sums the splits in
+    int tiles = 0, tps = 0;     // Winograd kinds: 2 x 2 output tiles, tiles per split
+    int nt = 1;                 // halo kinds: 64-channel output tiles per block
+    int tiles_w = 0, tiles_h = 0;   // direct kinds: pixel tiles of an image
+    size_t slab_bytes() const { return (size_t)splits * pages * Nr * pKcp * sizeof(float); }
+    size_t part_bytes() const { return G > 1 ? (size_t)G * Nr * Kcp * sizeof(double) : 0; }
+    size_t ws_bytes() const { return ((slab_bytes() + 255) / 256) * 256 + part_bytes(); }
+};
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+static bool same_3x3(const pu_wgrad_args* a) {
+    return a->kh == 3 && a->kw == 3 && a->stride == 1 && a->pad == 1 && a->in_h == a->out_h && a->in_w == a->out_w;
 }
 
-// phase 2 of every weight-gradient path: fixed-order fp64 reduction of the split partials and
+static bool stem_wgrad_ok(const pu_wgrad_args* a) {
+    return a->c0 == 1 && a->c1 == 0 && (a->n == 8 || a->n == 16 || a->n == 32 || a->n == 64) && same_3x3(a) &&
+           a->bias_mode == 1 && aligned16(a->rows);
+}
+
+// 1x1 / s1 / p0 same-size conv, one source, (C, N) an instantiated wgrad_pw_kernel pair
+static bool pw_wgrad_ok(const pu_wgrad_args* a) {
+    const int C = a->c0, N = a->n;
+    return a->c1 == 0 && a->kh == 1 && a->kw == 1 && a->stride == 1 && a->pad == 0 && a->in_h == a->out_h &&
+           a->in_w == a->out_w && a->bias_mode != 2 && (C == 3 || C == 4) && (N == 4 || N == 8 || N == 16) &&
+           aligned16(a->rows) && (C % 4 || aligned16(a->src0));
+}
+
+static bool small_wgrad_ok(const pu_wgrad_args* a) {
+    const int C = a->c0 + a->c1;
+    return (C == 1 || C == 4 || C == 8 || C == 12 || C == 16) && (a->n == 4 || a->n == 8 || a->n == 16) &&
+           same_3x3(a) && a->bias_mode != 2 && (C == 1 || (a->c0 % 4 == 0 && a->c1 % 4 == 0));
+}
+
+// the halo kernels: 3x3 / s1 / p1 same-size, 16-pixel stages within a row, 64-channel blocks
+static bool halo_wgrad_ok(const pu_wgrad_args* a, const WgradPlan* pl) {
+    return same_3x3(a) && a->out_w % 16 == 0 && a->c0 % 64 == 0 && a->c1 % 64 == 0 && a->n % 64 == 0 &&
+           a->bias_mode != 2 && (long long)pl->M * pl->C < (1LL << 31);
+}
+
+// the Winograd-domain kernels: 3x3 / s1 / p1 on an even same-size grid, 64-channel input blocks
+// from one source each, 64-channel output blocks, the 6-product arithmetic, byte offsets of the
+// (shifted) sources and of dZ under 2^31
+static bool wino_wgrad_ok(const pu_wgrad_args* a) {
+    if (a->math != 1 || !same_3x3(a) || (a->out_h & 1) || (a->out_w & 1)) return false;
+    if (a->c0 % 64 || a->c1 % 64 || a->n % 64 || a->bias_mode == 2) return false;
+    const long long px = (long long)a->batch * a->in_h * a->in_w + a->in_w + 1;
+    if (px * (a->c0 > a->c1 ? a->c0 : a->c1) * 4 >= (1LL << 31)) return false;
+    if ((long long)a->batch * a->out_h * a->out_w * a->n * 4 >= (1LL << 31)) return false;
+    return (((uintptr_t)a->rows | (uintptr_t)a->src0 | (uintptr_t)a->src1) & 7) == 0;
+}
+
+// Fewest tiles at which the column plan (wgrad_wino_cols_x6_kernel) is taken: C2's smallest qualifying
+// layers (the 8 x 8 level at batch 32) have 512; the measured gate is in DESIGN.md section 2.
+constexpr int WWR_MIN_TILES = 512;
+
+// reduction groups: one pass (1 group, each thread sums every split of its entry) when the result
+// has enough entries to fill the chip; otherwise groups of >= 8 splits each, then as many partials
+static int reduce_groups(long long total, int splits) {
+    int G = (int)ceil_div(262144LL, total);
+    const int by_len = ceil_div(splits, 8);
+    if (G > by_len) G = by_len;
+    if (G > 16) G = 16;
+    return G < 1 ? 1 : G;
+}
+
+// the GEMM's dimensions and the slab's shape, fp32 and bf16 alike: M pixel rows, K = taps x C,
+// Nr x Kc slab entries with the bias as row N (mode 2) or column K (mode 1).  Kcp, the slab's row
+// stride, is Kc rounded up to 4 floats: phase 2 reads and sums every slab as 16-byte quads.
+static int plan_dims(const pu_wgrad_args* a, WgradPlan* pl, const char* who) {
+    const long long M = (long long)a->batch * a->out_h * a->out_w;
+    PU_REQUIRE(M < (1LL << 31), "%s: too many pixels", who);
+    pl->M = (int)M;
+    pl->C = a->c0 + a->c1;
+    pl->K = a->kh * a->kw * pl->C;
+    pl->Nr = a->n + (a->bias_mode == 2 ? 1 : 0);
+    pl->Kc = pl->K + (a->bias_mode == 1 ? 1 : 0);
+    pl->Kcp = (pl->Kc + 3) / 4 * 4;
+    pl->pages = 1;
+    pl->pK = pl->K;
+    pl->pKc = pl->Kc;
+    pl->pKcp = pl->Kcp;
+    return PU_OK;
+}
+
+// the halo kernels (wgrad_halo_x6_kernel, wgrad_halo_bf16_kernel): 64 NT x 64 x 9-tap tiles,
+// 16-pixel stages split so that one round of blocks fills the chip
+static void plan_halo(const pu_wgrad_args* a, WgradKind kind, WgradPlan* pl) {
+    pl->kind = kind;
+    pl->nt = a->n % 128 == 0 ? 2 : 1;    // 128 output channels per block when they divide
+    pl->BN = 64 * pl->nt;
+    pl->BK = 9 * 64;
+    pl->gx = pl->C / 64;
+    pl->gy = a->n / pl->BN;
+    int splits = (pl->nt == 2 ? 256 : 512) / (pl->gx * pl->gy);   // one 8-wave / two 4-wave blocks per CU
+    const int stages = pl->M / 16;
+    if (splits > stages) splits = stages;
+    if (splits < 1) splits = 1;
+    pl->mps = ceil_div(stages, splits) * 16;
+    pl->splits = ceil_div(pl->M, pl->mps);
+}
+
+// the Winograd-domain kernels, one 512-thread block per CU: (C / cb) x (N / cb) channel blocks x
+// tile splits of whole 16-tile stages, with cb = 64, or with cb = 128 x 4 position columns when the
+// channels divide and there are tiles enough.  A column writes its own page of [Nr][3 C (+ 1 bias
+// column)] entries, and the finisher sums the splits in the groups the whole result would get.
+static void plan_wino(const pu_wgrad_args* a, WgradPlan* pl) {
+    pl->tiles = a->batch * (a->out_h / 2) * (a->out_w / 2);
+    const bool cols = a->c0 % 128 == 0 && a->c1 % 128 == 0 && a->n % 128 == 0 && pl->tiles >= WWR_MIN_TILES;
+    const int cb = cols ? 128 : 64;
+    pl->kind = cols ? WK_WINO_COLS : WK_WINO;
+    pl->BN = cb;
+    pl->BK = cols ? 3 * 128 : 9 * 64;
+    pl->gx = pl->C / cb;
+    pl->gy = a->n / cb;
+    const int stages = ceil_div(pl->tiles, 16);
+    int splits = 256 / ((cols ? 4 : 1) * pl->gx * pl->gy);
+    if (splits > stages) splits = stages;
+    if (splits < 1) splits = 1;
+    pl->tps = ceil_div(stages, splits) * 16;
+    pl->splits = ceil_div(pl->tiles, pl->tps);
+    pl->mps = pl->tps * 4;
+    if (cols) {
+        pl->pages = 4;
+        pl->pK = 3 * pl->C;
+        pl->pKc = pl->pK + (a->bias_mode == 1 ? 1 : 0);
+        pl->pKcp = (pl->pKc + 3) / 4 * 4;
+    }
+}
+
+// Measured alternatives: capping the GEMM-path split count at 2 / 4 (round 3: C2 4060 -> 2262 /
+// 2968 img/s - the deep layers' slab traffic is cheaper than idle CUs); round 1: 64 x 576 6-wave tiles for the 64-channel layers (-6 %), a
+// 3-wave 64 x 192 tile (-8 %), a split-once-planes kernel that still staged fp32 through LDS
+// (-10...-25 %); the halo kernel replaced all of them on 3x3/s1 layers.
+static void plan_f32(const pu_wgrad_args* a, WgradPlan* pl) {
+    const long long M = pl->M;
+    if (pw_wgrad_ok(a)) {              // pointwise: contiguous pixel ranges, one slab row block each
+        pl->kind = WK_PW;
+        pl->splits = (int)(M / 256 < 1024 ? (M + 255) / 256 : 1024);
+        pl->mps = (int)ceil_div(M, (long long)pl->splits);
+        pl->splits = (int)ceil_div(M, (long long)pl->mps);
+        pl->BN = a->n; pl->BK = pl->K; pl->gx = pl->gy = 1;
+        return;
+    }
+    if (stem_wgrad_ok(a) || small_wgrad_ok(a)) {   // direct kernels: one slab row block per block
+        const bool stem = stem_wgrad_ok(a);
+        pl->kind = stem ? WK_STEM : WK_SMALL;
+        pl->tiles_w = ceil_div(a->out_w, stem ? SWS_TW : SW_TW);
+        pl->tiles_h = ceil_div(a->out_h, stem ? SWS_TH : SW_TH);
+        const long long ntiles = (long long)a->batch * pl->tiles_w * pl->tiles_h;
+        pl->splits = (int)(ntiles < 1024 ? ntiles : 1024);
+        pl->BN = a->n; pl->BK = pl->K; pl->gx = pl->gy = 1; pl->mps = 0;
+        return;
+    }
+    if (wino_wgrad_ok(a)) return plan_wino(a, pl);
+    if (a->math == 1 && halo_wgrad_ok(a, pl)) return plan_halo(a, WK_HALO, pl);
+    // the direct-to-LDS kernel (float4 sources) tiles only the N x K GEMM (bias via LDS column
+    // sums); the register-staged kernel carries the bias as an extra ones column / row
+    const bool dma = a->c0 % 4 == 0 && a->c1 % 4 == 0;
+    pl->kind = dma ? WK_DMA : WK_REG;
+    pl->fq = dma && a->math == 1 && a->stride == 1 && a->in_h == a->out_h && a->in_w == a->out_w && a->out_w >= 4;
+    const int ext_n = dma ? a->n : pl->Nr;
+    const int ext_k = dma ? pl->K : pl->Kc;
+    int occ;  // resident blocks per CU (LDS / VGPR limited, from the resource-usage report)
+    if (ext_k <= 64) { pl->BN = 64; pl->BK = 64; occ = dma ? 6 : 7; }
+    else if (ext_n <= 64 && !dma) { pl->BN = 64; pl->BK = 256; occ = 3; }
+    else if (ext_n <= 32 && a->math == 1) { pl->BN = 32; pl->BK = 128; occ = 4; }   // 32-channel layers (C4/C5)
+    else if (ext_n <= 64) {
+        // BK 128 (4 resident blocks) unless 192 (3 resident) pads k less - e.g. K = 9 taps x 64
+        const bool b192 = ceil_div(ext_k, 192) * 192 < ceil_div(ext_k, 128) * 128;
+        pl->BN = 64; pl->BK = b192 ? 192 : 128; occ = b192 ? 3 : 4;
+    }
+    else { pl->BN = 128; pl->BK = 128; occ = dma ? 3 : 4; }
+    // 6-product path: a 128 x 256 tile (2x2 waves of 64 x 128) splits 6 operand fragments per 48
+    // MFMAs instead of 4 per 24, when K pads no worse than with 128
+    if (a->math == 1 && dma && pl->BN == 128 && ceil_div(ext_k, 256) * 256 <= ceil_div(ext_k, 128) * 128) {
+        pl->BK = 256;
+        occ = 2;
+    }
+    pl->gx = ceil_div(ext_k, pl->BK);
+    pl->gy = ceil_div(ext_n, pl->BN);
+    // one full round of resident blocks: a grid a few blocks past a multiple of the resident
+    // slots costs a whole extra round
+    int splits = 256 * occ / (pl->gx * pl->gy);
+    const int max_splits = ceil_div(M, 256);
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    pl->mps = ceil_div(ceil_div(M, splits), WG_BM) * WG_BM;
+    pl->splits = ceil_div(M, pl->mps);
+}
+
+// bf16: the halo kernel, or 128 x 128 tiles of the N x K GEMM (bias via LDS column sums), pixel rows
+// split so that one round of resident blocks (3 per CU: 48 KB ring) fills the chip
+static void plan_bf16(const pu_wgrad_args* a, WgradPlan* pl) {
+    if (halo_wgrad_ok(a, pl)) return plan_halo(a, WK_BF16_HALO, pl);
+    pl->kind = WK_BF16;
+    pl->BN = WB_W; pl->BK = WB_W;
+    pl->gx = ceil_div(pl->K, WB_W);
+    pl->gy = ceil_div(a->n, WB_W);
+    int splits = 768 / (pl->gx * pl->gy);
+    const int max_splits = ceil_div(pl->M, 512);
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    pl->mps = ceil_div(ceil_div(pl->M, splits), WB_ROWS) * WB_ROWS;
+    pl->splits = ceil_div(pl->M, pl->mps);
+}
+
+// Phase 2 of every weight-gradient path is a fixed-order fp64 reduction of the split partials and
 // the store into PyTorch's [n][c][kh][kw] (+ bias).
 // The one-launch wide reduction takes the direct small-channel / stem / pointwise plans (up to
 // 1024 splits of a few-thousand-entry slab) and the other non-Winograd plans whose slabs are short
@@ -2830,65 +2770,251 @@ static void launch_finisher(bool transposed, const T* part, int count, const Wgr
 // The split partials are summed in fp64 either way, in a different fixed order.
 constexpr long long WR_WIDE_MAX = 16384;
 
+static void plan_reducer(const pu_wgrad_args* a, WgradPlan* pl) {
+    const long long total = (long long)pl->Nr * pl->Kcp;
+    const int groups = reduce_groups(total, pl->splits);
+    const bool direct = pl->kind == WK_STEM || pl->kind == WK_PW || pl->kind == WK_SMALL;
+    pl->dw_vec = aligned16(a->dweight);
+    pl->transposed = a->bias_mode != 2 && a->kh * a->kw <= 9 && pl->C % 4 == 0 && pl->dw_vec;
+    pl->G = groups;
+    if (pl->kind == WK_WINO_COLS) {
+        pl->reducer = RD_COLS;
+        pl->fin_groups = groups;
+        pl->G = 1;                            // its partials stay in LDS: none in the workspace
+    } else if ((direct || (pl->kind != WK_WINO && total <= WR_WIDE_MAX)) && a->bias_mode != 2) {
+        pl->reducer = RD_WIDE;
+    } else {
+        pl->reducer = groups > 1 ? RD_GROUPS : RD_SPLITS;
+    }
+}
+
+// The two entries differ in what their kernels ask of n, c0 and c1, in the math argument (fp32
+// only) and in the tile choice.
+static int plan_wgrad(const pu_wgrad_args* a, bool bf16, WgradPlan* pl) {
+    const char* who = bf16 ? "pu_wgrad_bf16" : "pu_wgrad";
+    PU_REQUIRE(a && a->batch > 0 && a->out_h > 0 && a->out_w > 0 && a->in_h > 0 && a->in_w > 0, "%s: bad grid", who);
+    PU_REQUIRE(a->kh > 0 && a->kw > 0 && a->stride > 0 && a->pad >= 0, "%s: bad taps", who);
+    PU_REQUIRE(a->rows && a->n > 0 && a->src0 && a->c0 > 0 && (a->c1 == 0 || a->src1), "%s: operands", who);
+    if (bf16)
+        PU_REQUIRE(a->n % 8 == 0 && a->c0 % 8 == 0 && a->c1 % 8 == 0,
+                   "%s: n (%d) and channel counts (%d, %d) must be multiples of 8", who, a->n, a->c0, a->c1);
+    else
+        PU_REQUIRE(a->n % 4 == 0, "%s: n (%d) must be a multiple of 4", who, a->n);
+    PU_REQUIRE(a->bias_mode >= 0 && a->bias_mode <= 2, "%s: bias_mode", who);
+    PU_REQUIRE(a->bias_mode == 0 || a->dbias, "%s: dbias missing", who);
+    PU_REQUIRE(a->dweight, "%s: dweight missing", who);
+    if (!bf16) {
+        PU_REQUIRE(a->math >= 0 && a->math <= 2, "%s: math %d", who, a->math);
+        PU_REQUIRE(a->math != 2 || stem_wgrad_ok(a), "%s: math 2 (bf16 rows) is the single-channel stem only", who);
+    }
+    if (int st = plan_dims(a, pl, who)) return st;
+    if (bf16 || (a->c0 % 4 == 0 && a->c1 % 4 == 0))   // sources read as 16-byte quads
+        PU_REQUIRE(aligned16(a->src0) && aligned16(a->src1), "%s: sources must be 16-byte aligned", who);
+    PU_REQUIRE(aligned16(a->rows), "%s: rows must be 16-byte aligned", who);
+    if (bf16) plan_bf16(a, pl);
+    else plan_f32(a, pl);
+    plan_reducer(a, pl);
+    return PU_OK;
+}
+
+// the fields that WgradParams and WgradBf16Params share
+template <typename P>
+static void fill_params(const WgradPlan& pl, const pu_wgrad_args* a, void* workspace, P* p) {
+    p->M = pl.M; p->N = a->n; p->Nr = pl.Nr; p->K = pl.pK; p->Kcp = pl.pKcp; p->C = pl.C; p->c0 = a->c0; p->c1 = a->c1;
+    p->Hi = a->in_h; p->Wi = a->in_w; p->Ho = a->out_h; p->Wo = a->out_w;
+    p->kw = a->kw; p->stride = a->stride; p->pad = a->pad;
+    p->P = (decltype(p->P))a->rows; p->src0 = (decltype(p->src0))a->src0; p->src1 = (decltype(p->src1))a->src1;
+    p->bias_mode = a->bias_mode;
+    p->slab = (float*)workspace; p->mps = pl.mps; p->gx = pl.gx; p->gy = pl.gy;
+    p->dWo = make_fastdiv(a->out_w); p->dHo = make_fastdiv(a->out_h);
+    p->dC = make_fastdiv(pl.C); p->dKw = make_fastdiv(a->kw);
+}
+
+template <int N>
+static void launch_stem(bool bf16_rows, dim3 grid, hipStream_t s, const WgradParams& p) {
+    if (bf16_rows) hipLaunchKernelGGL((wgrad_stem_kernel<N, true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((wgrad_stem_kernel<N, false>), grid, dim3(256), 0, s, p);
+}
+
+// a DMA tile in the form the plan names: FQ, 6-product, or (PLAIN: where it is built) 3-product
+template <int BN, int BK, int WN, int WK, bool PLAIN = true>
+static void launch_dma(const WgradPlan& pl, bool x6, dim3 grid, hipStream_t s, const WgradParams& p) {
+    if (pl.fq) hipLaunchKernelGGL((wgrad_dma_kernel<BN, BK, WN, WK, 3, true, 4, true>), grid, dim3(256), 0, s, p);
+    else if (x6 || !PLAIN) hipLaunchKernelGGL((wgrad_dma_kernel<BN, BK, WN, WK, 3, true>), grid, dim3(256), 0, s, p);
+    else if constexpr (PLAIN) hipLaunchKernelGGL((wgrad_dma_kernel<BN, BK, WN, WK, 3, false>), grid, dim3(256), 0, s, p);
+}
+
+// phase 1: the plan's kernel writes the split partials into the slab
+static int wgrad_launch(const WgradPlan& pl, const pu_wgrad_args* a, void* workspace, hipStream_t s) {
+    const dim3 grid(pl.gx * pl.gy * pl.splits * pl.pages);
+    const int C = pl.C, N = a->n;
+    const char* what = "pu_wgrad (gemm)";
+    WgradParams p;             // the fp32 kinds'
+    WgradBf16Params b;         // the bf16 kinds'
+    if (pl.kind == WK_BF16 || pl.kind == WK_BF16_HALO) {
+        fill_params(pl, a, workspace, &b);
+    } else {
+        fill_params(pl, a, workspace, &p);
+        p.Kc = pl.pKc;
+        p.batch = a->batch; p.tiles_w = pl.tiles_w; p.tiles_h = pl.tiles_h;
+    }
+    switch (pl.kind) {
+    case WK_STEM:
+        what = "pu_wgrad (stem)";
+        if (N == 64) launch_stem<64>(a->math == 2, grid, s, p);
+        else if (N == 32) launch_stem<32>(a->math == 2, grid, s, p);
+        else if (N == 16) launch_stem<16>(a->math == 2, grid, s, p);
+        else launch_stem<8>(a->math == 2, grid, s, p);
+        break;
+    case WK_PW:
+        what = "pu_wgrad (pointwise)";
+#define PU_PW(C_, N_) if (C == C_ && N == N_) hipLaunchKernelGGL((wgrad_pw_kernel<C_, N_>), grid, dim3(256), 0, s, p)
+        PU_PW(3, 4); else PU_PW(3, 8); else PU_PW(3, 16); else PU_PW(4, 4); else PU_PW(4, 8); else PU_PW(4, 16);
+#undef PU_PW
+        break;
+    case WK_SMALL:
+        what = "pu_wgrad (small-channel)";
+#define PU_SW(C_, N_) if (C == C_ && N == N_) hipLaunchKernelGGL((wgrad_small_kernel<C_, N_>), grid, dim3(256), 0, s, p)
+        PU_SW(1, 4); else PU_SW(1, 8); else PU_SW(1, 16); else PU_SW(4, 4); else PU_SW(4, 8); else PU_SW(4, 16);
+        else PU_SW(8, 4); else PU_SW(8, 8); else PU_SW(8, 16); else PU_SW(12, 4); else PU_SW(12, 8);
+        else PU_SW(12, 16); else PU_SW(16, 4); else PU_SW(16, 8); else PU_SW(16, 16);
+#undef PU_SW
+        break;
+    case WK_WINO:
+    case WK_WINO_COLS: {
+        WinoWgradParams ww;
+        ww.p = p;
+        ww.tiles = pl.tiles;
+        ww.tps = pl.tps;
+        ww.dTw = make_fastdiv(a->out_w / 2);
+        ww.dTh = make_fastdiv(a->out_h / 2);
+        const long long px = (long long)a->batch * a->in_h * a->in_w + a->in_w + 1;
+        ww.x0_bytes = (unsigned)(px * a->c0 * 4);
+        ww.x1_bytes = (unsigned)(px * a->c1 * 4);
+        ww.p_bytes = (unsigned)((long long)pl.M * a->n * 4);
+        if (pl.kind == WK_WINO_COLS) hipLaunchKernelGGL(wgrad_wino_cols_x6_kernel, grid, dim3(512), 0, s, ww);
+        else hipLaunchKernelGGL(wgrad_wino_x6_kernel, grid, dim3(512), 0, s, ww);
+        break;
+    }
+    case WK_HALO:
+        if (pl.nt == 2) hipLaunchKernelGGL(wgrad_halo_x6_kernel<2>, grid, dim3(512), 0, s, p);
+        else hipLaunchKernelGGL(wgrad_halo_x6_kernel<1>, grid, dim3(256), 0, s, p);
+        break;
+    case WK_DMA:
+        if (pl.BK == 64) launch_dma<64, 64, 2, 2>(pl, a->math == 1, grid, s, p);
+        else if (pl.BN == 64 && pl.BK == 128) launch_dma<64, 128, 2, 2>(pl, a->math == 1, grid, s, p);
+        else if (pl.BN == 32) launch_dma<32, 128, 1, 4, false>(pl, true, grid, s, p);      // planned under math 1 only
+        else if (pl.BK == 192) launch_dma<64, 192, 2, 2>(pl, a->math == 1, grid, s, p);
+        else if (pl.BK == 256) launch_dma<128, 256, 2, 2, false>(pl, true, grid, s, p);    // likewise
+        else launch_dma<128, 128, 2, 2>(pl, a->math == 1, grid, s, p);
+        break;
+    case WK_REG:
+#define PU_WG_REG(BN_, BK_, WN_, WK_) hipLaunchKernelGGL((wgrad_kernel<BN_, BK_, WN_, WK_, false>), grid, dim3(256), 0, s, p)
+        if (pl.BK == 64) PU_WG_REG(64, 64, 2, 2);
+        else if (pl.BK == 256) PU_WG_REG(64, 256, 1, 4);
+        else PU_WG_REG(128, 128, 2, 2);
+#undef PU_WG_REG
+        break;
+    case WK_BF16:
+        what = "pu_wgrad_bf16 (gemm)";
+        hipLaunchKernelGGL(wgrad_bf16_kernel, grid, dim3(256), 0, s, b);
+        break;
+    case WK_BF16_HALO:
+        what = "pu_wgrad_bf16 (gemm)";
+        if (pl.nt == 2) hipLaunchKernelGGL(wgrad_halo_bf16_kernel<2>, grid, dim3(512), 0, s, b);
+        else hipLaunchKernelGGL(wgrad_halo_bf16_kernel<1>, grid, dim3(256), 0, s, b);
+        break;
+    }
+    return check_launch(what);
+}
+
+// the transposed (coalesced float4 stores) or the quad (scattered stores) finisher over `count`
+// partials: the fp32 slab's splits, or the fp64 partials of wgrad_sum_splits4_kernel
+template <typename T>
+static void launch_finisher(const T* part, int count, const WgradPlan& pl, const pu_wgrad_args* a, hipStream_t s) {
+    const int taps = a->kh * a->kw;
+    if (pl.transposed) {
+        hipLaunchKernelGGL(wgrad_finish_t_kernel<T>, dim3((unsigned)ceil_div(pl.C, 256), (unsigned)a->n),
+                           dim3((unsigned)(64 * taps)), 0, s, part, count, pl.Nr, pl.Kcp, pl.K, pl.C, taps, a->bias_mode,
+                           a->dweight, a->dbias, a->accumulate);
+        return;
+    }
+    const long long threads = (long long)pl.Nr * pl.Kcp / 4 + (a->bias_mode == 2 ? pl.C : 0);
+    hipLaunchKernelGGL(wgrad_finish4_kernel<T>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, part, count,
+                       pl.Nr, pl.Kcp, a->n, pl.K, pl.C, a->kh, a->kw, a->bias_mode, a->dweight, a->dbias, a->accumulate);
+}
+
+// phase 2: the plan's reduction of the slab into dweight (+ dbias)
 static int wgrad_reduce(const WgradPlan& pl, const pu_wgrad_args* a, void* workspace, hipStream_t s) {
     const long long total = (long long)pl.Nr * pl.Kcp;
     const float* slab = (const float*)workspace;
-    if (pl.cols) {                                    // 4 pages per tile split, combined by the finisher
-        const dim3 fg((unsigned)ceil_div(pl.C, 256), (unsigned)a->n);
-        const int vec = ((uintptr_t)a->dweight & 15) == 0;
-        hipLaunchKernelGGL(wgrad_finish_cols_kernel, fg, dim3(192 * pl.Gfin), 0, s, slab, pl.splits / 4, pl.Gfin, pl.Nr,
-                           pl.Kcp, pl.C, a->bias_mode, a->dweight, a->dbias, a->accumulate, vec);
-        return check_launch("pu_wgrad (reduce)");
-    }
-    if ((pl.small || pl.stem || pl.pw || (!pl.wino && total <= WR_WIDE_MAX)) && a->bias_mode != 2) {
+    switch (pl.reducer) {
+    case RD_COLS:
+        hipLaunchKernelGGL(wgrad_finish_cols_kernel, dim3((unsigned)ceil_div(pl.C, 256), (unsigned)a->n),
+                           dim3(192 * pl.fin_groups), 0, s, slab, pl.splits, pl.fin_groups, pl.Nr, pl.pKcp, pl.C,
+                           a->bias_mode, a->dweight, a->dbias, a->accumulate, (int)pl.dw_vec);
+        break;
+    case RD_WIDE:
         hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)ceil_div(total, (long long)WR_E)), dim3(256), 0, s,
                            slab, pl.splits, total, a->n, pl.Kcp, pl.K, pl.C, a->kh, a->kw, a->bias_mode, a->dweight,
                            a->dbias, a->accumulate);
-        return check_launch("pu_wgrad (reduce)");
-    }
-    const bool transposed = a->bias_mode != 2 && a->kh * a->kw <= 9 && pl.C % 4 == 0 && ((uintptr_t)a->dweight & 15) == 0;
-    if (pl.G > 1) {
+        break;
+    case RD_SPLITS:
+        launch_finisher(slab, pl.splits, pl, a, s);
+        break;
+    case RD_GROUPS: {
         double* part = (double*)((char*)workspace + ((pl.slab_bytes() + 255) / 256) * 256);
         hipLaunchKernelGGL(wgrad_sum_splits4_kernel, dim3((unsigned)((total / 4 + 255) / 256), pl.G), dim3(256), 0, s,
                            slab, pl.splits, total, pl.G, part);
-        launch_finisher(transposed, (const double*)part, pl.G, pl, a, s);
-    } else {
-        launch_finisher(transposed, slab, pl.splits, pl, a, s);
+        launch_finisher((const double*)part, pl.G, pl, a, s);
+        break;
+    }
     }
     return check_launch("pu_wgrad (reduce)");
 }
 
-// bf16 plan: 128 x 128 tiles of the N x K GEMM (bias via LDS column sums), pixel rows split so
-// that one round of resident blocks (3 per CU: 48 KB ring) fills the chip
-static int plan_wgrad_bf16(const pu_wgrad_args* a, WgradPlan* pl) {
-    PU_REQUIRE(a && a->batch > 0 && a->out_h > 0 && a->out_w > 0 && a->in_h > 0 && a->in_w > 0, "pu_wgrad_bf16: bad grid");
-    PU_REQUIRE(a->kh > 0 && a->kw > 0 && a->stride > 0 && a->pad >= 0, "pu_wgrad_bf16: bad taps");
-    PU_REQUIRE(a->rows && a->n > 0 && a->src0 && a->c0 > 0 && (a->c1 == 0 || a->src1), "pu_wgrad_bf16: operands");
-    PU_REQUIRE(a->n % 8 == 0 && a->c0 % 8 == 0 && a->c1 % 8 == 0,
-               "pu_wgrad_bf16: n (%d) and channel counts (%d, %d) must be multiples of 8", a->n, a->c0, a->c1);
-    PU_REQUIRE(a->bias_mode >= 0 && a->bias_mode <= 2 && (a->bias_mode == 0 || a->dbias) && a->dweight, "pu_wgrad_bf16: outputs");
-    PU_REQUIRE((((uintptr_t)a->rows | (uintptr_t)a->src0 | (uintptr_t)a->src1) & 15) == 0, "pu_wgrad_bf16: 16-byte alignment");
-    if (int st = plan_dims(a, pl, "pu_wgrad_bf16")) return st;
-    const long long M = pl->M;
-    pl->qvec = true; pl->dma = true; pl->small = false; pl->stem = false;
-    pl->halo = false;
-    if (a->kh == 3 && a->kw == 3 && a->stride == 1 && a->pad == 1 && a->in_h == a->out_h &&
-        a->in_w == a->out_w && a->out_w % 16 == 0 && a->c0 % 64 == 0 && a->c1 % 64 == 0 && a->n % 64 == 0 &&
-        a->bias_mode != 2 && M * pl->C < (1LL << 31)) {
-        plan_halo(a, pl);
-        return PU_OK;
+static int run_wgrad(const pu_wgrad_args* a, bool bf16, void* workspace, size_t ws_bytes, int phase, void* stream) {
+    const char* who = bf16 ? "pu_wgrad_bf16" : "pu_wgrad";
+    PU_REQUIRE(phase >= 1 && phase <= 3, "%s_phase: phase %d", who, phase);
+    WgradPlan pl;
+    if (int st = plan_wgrad(a, bf16, &pl)) return st;
+    const size_t need = pl.ws_bytes();
+    if (!workspace || ws_bytes < need) return fail(PU_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    hipStream_t s = as_stream(stream);
+    if (phase & 1)
+        if (int st = wgrad_launch(pl, a, workspace, s)) return st;
+    return (phase & 2) ? wgrad_reduce(pl, a, workspace, s) : PU_OK;
+}
+
+static size_t wgrad_workspace_bytes(const pu_wgrad_args* a, bool bf16) {
+    WgradPlan pl;
+    return plan_wgrad(a, bf16, &pl) == PU_OK ? pl.ws_bytes() : 0;
+}
+
+// the tile queries' third value: which kind of kernel the plan names (plastic_unet.h)
+static int tile_code(WgradKind kind) {
+    switch (kind) {
+    case WK_REG: return 0;
+    case WK_DMA: return 1;
+    case WK_SMALL: return 2;
+    case WK_HALO: return 3;
+    case WK_STEM: return 4;
+    case WK_WINO:
+    case WK_WINO_COLS: return 5;
+    case WK_PW: return 6;
+    case WK_BF16: return 0;
+    case WK_BF16_HALO: return 1;
     }
-    pl->BN = WB_W; pl->BK = WB_W;
-    pl->gx = ceil_div(pl->K, WB_W);
-    pl->gy = ceil_div(a->n, WB_W);
-    const int tiles = pl->gx * pl->gy;
-    int splits = 768 / tiles;
-    const int max_splits = ceil_div(M, 512);
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    pl->mps = ceil_div(ceil_div(M, splits), WB_ROWS) * WB_ROWS;
-    pl->splits = ceil_div(M, pl->mps);
-    plan_groups(pl);
+    return -1;
+}
+
+static int wgrad_tile(const pu_wgrad_args* a, bool bf16, int* bn, int* bk, int* code, int* splits) {
+    WgradPlan pl;
+    if (int st = plan_wgrad(a, bf16, &pl)) return st;
+    if (bn) *bn = pl.BN;
+    if (bk) *bk = pl.BK;
+    if (code) *code = tile_code(pl.kind);
+    if (splits) *splits = pl.splits * pl.pages;
     return PU_OK;
 }
 
@@ -2896,188 +3022,30 @@ static int plan_wgrad_bf16(const pu_wgrad_args* a, WgradPlan* pl) {
 
 using namespace pu;
 
-extern "C" size_t pu_wgrad_workspace_bytes(const pu_wgrad_args* a) {
-    WgradPlan pl;
-    if (plan_wgrad(a, &pl) != PU_OK) return 0;
-    return pl.ws_bytes();
-}
+extern "C" size_t pu_wgrad_workspace_bytes(const pu_wgrad_args* a) { return wgrad_workspace_bytes(a, false); }
 
 extern "C" int pu_wgrad_tile(const pu_wgrad_args* a, int* bn, int* bk, int* qvec, int* splits) {
-    WgradPlan pl;
-    int st = plan_wgrad(a, &pl);
-    if (st != PU_OK) return st;
-    if (bn) *bn = pl.BN;
-    if (bk) *bk = pl.BK;
-    if (qvec) *qvec = pl.pw ? 6 : pl.wino ? 5 : pl.stem ? 4 : pl.small ? 2 : pl.halo ? 3 : (pl.qvec ? 1 : 0);   // 2: small-channel direct, 3: halo, 4: stem, 5: Winograd, 6: pointwise
-    if (splits) *splits = pl.splits;
-    return PU_OK;
+    return wgrad_tile(a, false, bn, bk, qvec, splits);
 }
 
 extern "C" int pu_wgrad(const pu_wgrad_args* a, void* workspace, size_t ws_bytes, void* stream) {
-    return pu_wgrad_phase(a, workspace, ws_bytes, 3, stream);
+    return run_wgrad(a, false, workspace, ws_bytes, 3, stream);
 }
 
 extern "C" int pu_wgrad_phase(const pu_wgrad_args* a, void* workspace, size_t ws_bytes, int phase, void* stream) {
-    PU_REQUIRE(phase >= 1 && phase <= 3, "pu_wgrad_phase: phase %d", phase);
-    WgradPlan pl;
-    int st = plan_wgrad(a, &pl);
-    if (st != PU_OK) return st;
-    const size_t need = pl.ws_bytes();
-    if (!workspace || ws_bytes < need)
-        return fail(PU_ERR_WORKSPACE, "pu_wgrad: workspace %zu < %zu bytes", ws_bytes, need);
-
-    WgradParams p;
-    p.M = pl.M; p.N = a->n; p.Nr = pl.Nr; p.K = pl.K; p.Kc = pl.Kc; p.Kcp = pl.Kcp; p.C = pl.C; p.c0 = a->c0; p.c1 = a->c1;
-    p.Hi = a->in_h; p.Wi = a->in_w; p.Ho = a->out_h; p.Wo = a->out_w;
-    p.kw = a->kw; p.stride = a->stride; p.pad = a->pad;
-    p.P = a->rows; p.src0 = a->src0; p.src1 = a->src1; p.bias_mode = a->bias_mode;
-    p.slab = (float*)workspace; p.mps = pl.mps;
-    p.dWo = make_fastdiv(a->out_w); p.dHo = make_fastdiv(a->out_h);
-    p.dC = make_fastdiv(pl.C); p.dKw = make_fastdiv(a->kw);
-
-    hipStream_t s = as_stream(stream);
-    p.gx = pl.gx;
-    p.gy = pl.gy;
-    p.batch = a->batch; p.tiles_w = pl.tiles_w; p.tiles_h = pl.tiles_h;
-    if (pl.stem && (phase & 1) && a->math == 2) {
-        if (a->n == 64) hipLaunchKernelGGL((wgrad_stem_kernel<64, true>), dim3(pl.splits), dim3(256), 0, s, p);
-        else if (a->n == 32) hipLaunchKernelGGL((wgrad_stem_kernel<32, true>), dim3(pl.splits), dim3(256), 0, s, p);
-        else if (a->n == 16) hipLaunchKernelGGL((wgrad_stem_kernel<16, true>), dim3(pl.splits), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((wgrad_stem_kernel<8, true>), dim3(pl.splits), dim3(256), 0, s, p);
-        st = check_launch("pu_wgrad (stem, bf16 rows)");
-        if (st != PU_OK) return st;
-        phase &= ~1;
-    }
-    if (pl.stem && (phase & 1)) {
-        if (a->n == 64) hipLaunchKernelGGL(wgrad_stem_kernel<64>, dim3(pl.splits), dim3(256), 0, s, p);
-        else if (a->n == 32) hipLaunchKernelGGL(wgrad_stem_kernel<32>, dim3(pl.splits), dim3(256), 0, s, p);
-        else if (a->n == 16) hipLaunchKernelGGL(wgrad_stem_kernel<16>, dim3(pl.splits), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(wgrad_stem_kernel<8>, dim3(pl.splits), dim3(256), 0, s, p);
-        st = check_launch("pu_wgrad (stem)");
-        if (st != PU_OK) return st;
-        phase &= ~1;
-    }
-    if (pl.pw && (phase & 1)) {
-        const int C = pl.C, N = a->n;
-        const dim3 sg(pl.splits);
-#define PU_PW(C_, N_) if (C == C_ && N == N_) hipLaunchKernelGGL((wgrad_pw_kernel<C_, N_>), sg, dim3(256), 0, s, p)
-        PU_PW(3, 4); else PU_PW(3, 8); else PU_PW(3, 16); else PU_PW(4, 4); else PU_PW(4, 8); else PU_PW(4, 16);
-#undef PU_PW
-        st = check_launch("pu_wgrad (pointwise)");
-        if (st != PU_OK) return st;
-        phase &= ~1;
-    }
-    if (pl.small && (phase & 1)) {
-        const int C = pl.C, N = a->n;
-        const dim3 sg(pl.splits);
-#define PU_SW(C_, N_) if (C == C_ && N == N_) hipLaunchKernelGGL((wgrad_small_kernel<C_, N_>), sg, dim3(256), 0, s, p)
-        PU_SW(1, 4); else PU_SW(1, 8); else PU_SW(1, 16); else PU_SW(4, 4); else PU_SW(4, 8); else PU_SW(4, 16);
-        else PU_SW(8, 4); else PU_SW(8, 8); else PU_SW(8, 16); else PU_SW(12, 4); else PU_SW(12, 8);
-        else PU_SW(12, 16); else PU_SW(16, 4); else PU_SW(16, 8); else PU_SW(16, 16);
-#undef PU_SW
-        st = check_launch("pu_wgrad (small-channel)");
-        if (st != PU_OK) return st;
-        phase &= ~1;
-    }
-    dim3 grid(p.gx * p.gy * pl.splits);
-    const bool fq = a->stride == 1 && a->in_h == a->out_h && a->in_w == a->out_w && a->out_w >= 4;
-    if (phase & 1) {
-#define PU_WG_DMA(BN_, BK_, WN_, WK_)                                                                    \
-    do {                                                                                                     \
-        if (a->math == 1 && fq) hipLaunchKernelGGL((wgrad_dma_kernel<BN_, BK_, WN_, WK_, 3, true, 4, true>), grid, dim3(256), 0, s, p); \
-        else if (a->math == 1) hipLaunchKernelGGL((wgrad_dma_kernel<BN_, BK_, WN_, WK_, 3, true>), grid, dim3(256), 0, s, p); \
-        else hipLaunchKernelGGL((wgrad_dma_kernel<BN_, BK_, WN_, WK_, 3, false>), grid, dim3(256), 0, s, p); \
-    } while (0)
-#define PU_WG_REG(BN_, BK_, WN_, WK_) hipLaunchKernelGGL((wgrad_kernel<BN_, BK_, WN_, WK_, false>), grid, dim3(256), 0, s, p)
-        if (pl.wino) {
-            WinoWgradParams ww;
-            ww.p = p;
-            ww.tiles = pl.tiles;
-            ww.tps = pl.tps;
-            ww.dTw = make_fastdiv(a->out_w / 2);
-            ww.dTh = make_fastdiv(a->out_h / 2);
-            const long long px = (long long)a->batch * a->in_h * a->in_w + a->in_w + 1;
-            ww.x0_bytes = (unsigned)(px * a->c0 * 4);
-            ww.x1_bytes = (unsigned)(px * a->c1 * 4);
-            ww.p_bytes = (unsigned)((long long)pl.M * a->n * 4);
-            if (pl.cols) {
-                ww.p.K = 3 * pl.C;            // the bias column of a row page
-                hipLaunchKernelGGL(wgrad_wino_cols_x6_kernel, grid, dim3(512), 0, s, ww);
-            } else {
-                hipLaunchKernelGGL(wgrad_wino_x6_kernel, grid, dim3(512), 0, s, ww);
-            }
-        } else if (pl.halo) {
-            if (pl.nt == 2) hipLaunchKernelGGL(wgrad_halo_x6_kernel<2>, grid, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL(wgrad_halo_x6_kernel<1>, grid, dim3(256), 0, s, p);
-        } else if (pl.dma) {
-            if (pl.BK == 64) PU_WG_DMA(64, 64, 2, 2);
-            else if (pl.BN == 64 && pl.BK == 128) PU_WG_DMA(64, 128, 2, 2);
-            else if (pl.BN == 32 && fq) hipLaunchKernelGGL((wgrad_dma_kernel<32, 128, 1, 4, 3, true, 4, true>), grid, dim3(256), 0, s, p);   // planned under math 1 only
-            else if (pl.BN == 32) hipLaunchKernelGGL((wgrad_dma_kernel<32, 128, 1, 4, 3, true>), grid, dim3(256), 0, s, p);
-            else if (pl.BK == 192) PU_WG_DMA(64, 192, 2, 2);
-            else if (pl.BK == 256 && fq) hipLaunchKernelGGL((wgrad_dma_kernel<128, 256, 2, 2, 3, true, 4, true>), grid, dim3(256), 0, s, p);
-            else if (pl.BK == 256) hipLaunchKernelGGL((wgrad_dma_kernel<128, 256, 2, 2, 3, true>), grid, dim3(256), 0, s, p);
-            else PU_WG_DMA(128, 128, 2, 2);
-        } else {                              // pl.dma == pl.qvec: the register-staged kernel is the scalar loader's
-            if (pl.BK == 64) PU_WG_REG(64, 64, 2, 2);
-            else if (pl.BK == 256) PU_WG_REG(64, 256, 1, 4);
-            else PU_WG_REG(128, 128, 2, 2);
-        }
-#undef PU_WG_DMA
-#undef PU_WG_REG
-        st = check_launch("pu_wgrad (gemm)");
-        if (st != PU_OK) return st;
-    }
-    if (!(phase & 2)) return PU_OK;
-    return wgrad_reduce(pl, a, workspace, s);
+    return run_wgrad(a, false, workspace, ws_bytes, phase, stream);
 }
 
-extern "C" size_t pu_wgrad_bf16_workspace_bytes(const pu_wgrad_args* a) {
-    WgradPlan pl;
-    if (plan_wgrad_bf16(a, &pl) != PU_OK) return 0;
-    return pl.ws_bytes();
-}
-
-extern "C" int pu_wgrad_bf16_phase(const pu_wgrad_args* a, void* workspace, size_t ws_bytes, int phase, void* stream) {
-    PU_REQUIRE(phase >= 1 && phase <= 3, "pu_wgrad_bf16_phase: phase %d", phase);
-    WgradPlan pl;
-    int st = plan_wgrad_bf16(a, &pl);
-    if (st != PU_OK) return st;
-    const size_t need = pl.ws_bytes();
-    if (!workspace || ws_bytes < need)
-        return fail(PU_ERR_WORKSPACE, "pu_wgrad_bf16: workspace %zu < %zu bytes", ws_bytes, need);
-    hipStream_t s = as_stream(stream);
-    if (phase & 1) {
-        WgradBf16Params p;
-        p.M = pl.M; p.N = a->n; p.K = pl.K; p.Kcp = pl.Kcp; p.Nr = pl.Nr; p.C = pl.C; p.c0 = a->c0; p.c1 = a->c1;
-        p.Hi = a->in_h; p.Wi = a->in_w; p.Ho = a->out_h; p.Wo = a->out_w;
-        p.kw = a->kw; p.stride = a->stride; p.pad = a->pad;
-        p.P = (const __bf16*)a->rows; p.src0 = (const __bf16*)a->src0; p.src1 = (const __bf16*)a->src1;
-        p.bias_mode = a->bias_mode;
-        p.slab = (float*)workspace; p.mps = pl.mps; p.gx = pl.gx; p.gy = pl.gy;
-        p.dWo = make_fastdiv(a->out_w); p.dHo = make_fastdiv(a->out_h);
-        p.dC = make_fastdiv(pl.C); p.dKw = make_fastdiv(a->kw);
-        if (pl.halo && pl.nt == 2) hipLaunchKernelGGL(wgrad_halo_bf16_kernel<2>, dim3(pl.gx * pl.gy * pl.splits), dim3(512), 0, s, p);
-        else if (pl.halo) hipLaunchKernelGGL(wgrad_halo_bf16_kernel<1>, dim3(pl.gx * pl.gy * pl.splits), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(wgrad_bf16_kernel, dim3(pl.gx * pl.gy * pl.splits), dim3(256), 0, s, p);
-        st = check_launch("pu_wgrad_bf16 (gemm)");
-        if (st != PU_OK) return st;
-    }
-    if (!(phase & 2)) return PU_OK;
-    return wgrad_reduce(pl, a, workspace, s);
-}
+extern "C" size_t pu_wgrad_bf16_workspace_bytes(const pu_wgrad_args* a) { return wgrad_workspace_bytes(a, true); }
 
 extern "C" int pu_wgrad_bf16_tile(const pu_wgrad_args* a, int* bn, int* bk, int* halo, int* splits) {
-    WgradPlan pl;
-    int st = plan_wgrad_bf16(a, &pl);
-    if (st != PU_OK) return st;
-    if (bn) *bn = pl.BN;
-    if (bk) *bk = pl.BK;
-    if (halo) *halo = pl.halo ? 1 : 0;
-    if (splits) *splits = pl.splits;
-    return PU_OK;
+    return wgrad_tile(a, true, bn, bk, halo, splits);
 }
 
 extern "C" int pu_wgrad_bf16(const pu_wgrad_args* a, void* workspace, size_t ws_bytes, void* stream) {
-    return pu_wgrad_bf16_phase(a, workspace, ws_bytes, 3, stream);
+    return run_wgrad(a, true, workspace, ws_bytes, 3, stream);
+}
+
+extern "C" int pu_wgrad_bf16_phase(const pu_wgrad_args* a, void* workspace, size_t ws_bytes, int phase, void* stream) {
+    return run_wgrad(a, true, workspace, ws_bytes, phase, stream);
 }

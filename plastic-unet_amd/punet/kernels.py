@@ -332,42 +332,28 @@ def wgrad(*, batch, in_hw, out_hw, k, stride, pad, rows, n, src0, c0, dweight, s
     a = wgrad_args(batch=batch, in_hw=in_hw, out_hw=out_hw, k=k, stride=stride, pad=pad, rows=_p(rows), n=n,
                    src0=_p(src0), c0=c0, src1=_p(src1), c1=c1, bias_mode=bias_mode, dweight=_p(dweight),
                    dbias=_p(dbias), accumulate=accumulate, math=2 if stem_bf16 else 0 if dt == BF16 else None)
-    L = lib()
-    if dt == BF16:
-        nbytes = L.pu_wgrad_bf16_workspace_bytes(ctypes.byref(a))
-        ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=rows.device)
-        if nbytes == 0 or _PROF is None:
-            check(L.pu_wgrad_bf16(ctypes.byref(a), ws.data_ptr(), nbytes, _stream()), "pu_wgrad_bf16")
-            return
-        M = batch * out_hw[0] * out_hw[1]
-        bn, bk, hl = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        check(L.pu_wgrad_bf16_tile(ctypes.byref(a), ctypes.byref(bn), ctypes.byref(bk), ctypes.byref(hl), None),
-              "pu_wgrad_bf16_tile")
-        tag = "wgrad_bf16<%dx%d%s>" % (bn.value, bk.value, ",halo" if hl.value else "")
-        with _Rec(tag, flops=2.0 * M * n * k * k * (c0 + c1)):
-            check(L.pu_wgrad_bf16_phase(ctypes.byref(a), ws.data_ptr(), nbytes, 1, _stream()), "pu_wgrad_bf16")
-        with _Rec("wgrad_reduce", nbytes=float(nbytes)):
-            check(L.pu_wgrad_bf16_phase(ctypes.byref(a), ws.data_ptr(), nbytes, 2, _stream()), "pu_wgrad_bf16")
-        return
-    nbytes = L.pu_wgrad_workspace_bytes(ctypes.byref(a))
-    if nbytes == 0:
-        check(L.pu_wgrad(ctypes.byref(a), None, 0, _stream()), "pu_wgrad")
-        return
+    name = "pu_wgrad_bf16" if dt == BF16 else "pu_wgrad"
+    run, phase, tile, ws_bytes = (getattr(lib(), name + sfx) for sfx in ("", "_phase", "_tile", "_workspace_bytes"))
+    nbytes = ws_bytes(ctypes.byref(a))
     ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=rows.device)
-    if _PROF is None:
-        check(L.pu_wgrad(ctypes.byref(a), ws.data_ptr(), nbytes, _stream()), "pu_wgrad")
+    if nbytes == 0 or _PROF is None:          # (0: the arguments were refused, and run says why)
+        check(run(ctypes.byref(a), ws.data_ptr(), nbytes, _stream()), name)
         return
-    bn, bk, qv, sp = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    L.pu_wgrad_tile(ctypes.byref(a), ctypes.byref(bn), ctypes.byref(bk), ctypes.byref(qv), ctypes.byref(sp))
+    bn, bk, kind = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(tile(ctypes.byref(a), ctypes.byref(bn), ctypes.byref(bk), ctypes.byref(kind), None), name + "_tile")
+    if dt == BF16:
+        tag = "wgrad_bf16<%dx%d%s>" % (bn.value, bk.value, ",halo" if kind.value else "")
+    else:
+        tag = "wgrad<%dx%d,%s>" % (bn.value, bk.value,
+                                   ("scalar", "vec4", "direct", "halo", "stem", "wino", "pointwise")[kind.value])
+        if a.math == 1 and kind.value in (1, 3, 5):
+            tag = tag[:-1] + ",x6>"
     M = batch * out_hw[0] * out_hw[1]
-    tag = "wgrad<%dx%d,%s>" % (bn.value, bk.value, ("scalar", "vec4", "direct", "halo", "stem", "wino", "pointwise")[qv.value])
-    if a.math == 1 and qv.value in (1, 3, 5):
-        tag = tag[:-1] + ",x6>"
     # the GEMM and the split reduction timed apart (they are separate kernels in rocprof too)
     with _Rec(tag, flops=2.0 * M * n * k * k * (c0 + c1)):
-        check(L.pu_wgrad_phase(ctypes.byref(a), ws.data_ptr(), nbytes, 1, _stream()), "pu_wgrad_phase")
+        check(phase(ctypes.byref(a), ws.data_ptr(), nbytes, 1, _stream()), name + "_phase")
     with _Rec("wgrad_reduce", nbytes=float(nbytes)):
-        check(L.pu_wgrad_phase(ctypes.byref(a), ws.data_ptr(), nbytes, 2, _stream()), "pu_wgrad_phase")
+        check(phase(ctypes.byref(a), ws.data_ptr(), nbytes, 2, _stream()), name + "_phase")
 
 
 def wgrad_kind(*, batch, hw, n, c0, c1=0, k=3):

@@ -35,8 +35,6 @@ NAMES = [c.name for c in W.CASES]
 
 @pytest.mark.parametrize("name", NAMES)
 def test_row_plans_the_kernel_it_claims(name):
-    assert "PU_WINO_WGRAD" not in os.environ, \
-        "PU_WINO_WGRAD is set: the library reads it once per process and it moves the Winograd rows off their kernels"
     c = W.CASE[name]
     fs = W.forms(c)
     assert fs and {f.bias for _, f in fs} == set(W.PLANS[name])

@@ -1,5 +1,5 @@
 """CPU checks of the weight-gradient plan around the column form of the Winograd-domain kernel
-(csrc/wgrad.hip plan_wgrad): planning queries only, with stand-in pointers that nothing dereferences.
+(csrc/wgrad.hip plan_wino): planning queries only, with stand-in pointers that nothing dereferences.
 
 1. C2: the plan of every 3x3 weight-gradient call of UNetp(depth 5, base 64) on 128 x 128 images at
    batch 32.  The eleven layers whose channel counts are multiples of 128 take the plan of one

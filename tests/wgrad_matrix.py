@@ -5,8 +5,8 @@ test_wgrad_matrix_gpu.py.
 pu_wgrad / pu_wgrad_bf16 (csrc/wgrad.hip) run in two phases: phase 1, one of about sixty GEMM kernel
 instantiations, leaves `splits` partial [Nr][Kcp] tiles in the workspace; phase 2 sums them in fp64
 and stores dweight[n][c][kh][kw] (+ dbias).  Phase 2 has its own tests (test_wgrad_reduce_gpu.py,
-test_wgrad_rows_reduce_gpu.py); this matrix is about phase 1.  CASES has one row per launch branch
-of pu_wgrad_phase / pu_wgrad_bf16_phase, steered only by what a call passes (math, the grid, the
+test_wgrad_rows_reduce_gpu.py); this matrix is about phase 1.  CASES has one row per kernel
+instantiation the launcher's switch on the plan's kind can reach (wgrad_launch), steered only by what a call passes (math, the grid, the
 channel counts, kernel / stride / pad, alignment) - never by a process-wide switch - with the plan
 the library's queries report for it (PLANS) and the kernel instantiation that plan launches
 (kernel_of: the launcher's rule, which adds math, FQ, nt, the column form and the instantiated
@@ -79,7 +79,7 @@ WR_WIDE_MAX = 16384           # csrc/wgrad.hip: slabs of at most this many entri
 
 
 def reducer(c, bias, view):
-    """csrc/wgrad.hip wgrad_reduce: the phase-2 kernel a call takes"""
+    """csrc/wgrad.hip plan_reducer: the phase-2 kernel a call takes"""
     bn, bk, kind, _, _ = PLANS[c.name][bias]
     C = c.c0 + c.c1
     k = geometry(c)[2]
@@ -361,13 +361,13 @@ def pixels(c):
 
 
 def fq(c):
-    """the launcher's rule for the FQ forms of the math-1 kernels"""
+    """the planner's rule for the FQ forms of the math-1 kernels"""
     (ih, iw), (oh, ow), _, st, _ = geometry(c)
     return st == 1 and (ih, iw) == (oh, ow) and ow >= 4
 
 
 def kernel_of(c, bias):
-    """The instantiation pu_wgrad_phase / pu_wgrad_bf16_phase launches for the row's pinned plan."""
+    """The instantiation the launcher (csrc/wgrad.hip wgrad_launch) starts for the row's pinned plan."""
     bn, bk, kind, _, _ = PLANS[c.name][bias]
     C = c.c0 + c.c1
     if c.entry == "bf16":

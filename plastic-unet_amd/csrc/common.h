@@ -74,6 +74,18 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t x, const FastDiv& f) {
 
 inline int ceil_div(long long a, long long b) { return int((a + b - 1) / b); }
 
+// compute units of the current device (cached per device; 256 when the query fails)
+inline int device_cus() {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!cus[dev]) {
+        int n = 0;
+        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8) ? n : 256;
+    }
+    return cus[dev];
+}
+
 // ------------------------------------- tile and split-K choice of the tiled implicit-GEMM kernels
 // (igemm.hip's igemm_kernel / igemm_dma_kernel, igemm_bf16.hip's igemm_bf16_kernel)
 inline int blocks_for(long long M, int N, int bm, int bn) { return ceil_div(M, bm) * ceil_div(N, bn); }
@@ -136,7 +148,12 @@ __device__ __forceinline__ void static_for(F&& f) {
 // lean implicit-GEMM loaders: an out-of-image tap gets this byte offset, outside every buffer
 // descriptor's range, so the range check writes zeros into LDS (probed: tools/probes/oob_lds.hip)
 constexpr unsigned LEAN_OOB = 0x80000000u;
+
+// vector and address-space types of the MFMA kernels (igemm.hip, igemm_bf16.hip, wgrad.hip, ...)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void lds_void_t;
+typedef __attribute__((address_space(1))) const void gbl_void_t;
 
 // buffer_load_dwordx4 ... lds of 16 B per lane through a descriptor built from wave-uniform
 // inputs, made provably uniform (no waterfall loops around the loads); bytes == 0 drops every

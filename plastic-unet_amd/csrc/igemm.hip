@@ -62,146 +62,9 @@ __device__ __forceinline__ f32x4 load_a4(const IgemmParams& p, int pb, int hb, i
 }
 
 
-// The epilogue's two common forms - bias (+ReLU), the forward, or masks (+ReLU), the data
-// gradient, into one or two NHWC destinations - with every operand load issued before the first
-// store.  gfx9's vmcnt counts stores as well as loads, and epi_store4 loads each output's operand
-// right before its store: the wait for that load then also waited out the round trip of every
-// store before it, one store latency per output.  Operands and stores go through buffer
-// descriptors with 32-bit offsets (a 32-column fragment lies in one destination: n0 % 32 == 0,
-// so the descriptor is wave-uniform per fragment); lanes past M / N load zeros and drop their
-// stores (out-of-range offsets), so no per-lane branch splits the batch.  The bias is per channel:
-// MASK == false reads it per fragment column group.  Same operations in the same order as
-// epi_store4 (bias, ReLU, mask).
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t epi_rsrc(const void* base, bool on) {
-    const unsigned long long b = (unsigned long long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    void* ub = (void*)(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(ub, 0, on ? 0x7fffffff : 0, 0x00020000);
-}
-
-template <bool MASK, int FM, int FN>
-__device__ __forceinline__ void epilogue_batched(const IgemmParams& p, f32x16 (&acc)[FM][FN], int m0, int nc0, int lr,
-                                                 int lh) {
-    const bool relu = p.flags & PU_EPI_RELU;
-    const int n1 = p.N - p.n0;
-    unsigned orow[FM][FN];             // byte offset of (row m, fragment column 0), LEAN_OOB past M
-    bool first[FN];
-#pragma unroll
-    for (int j = 0; j < FN; ++j) first[j] = nc0 + j * 32 < p.n0;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-        const int m = m0 + i * 32 + lr;
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-            const int c = nc0 + j * 32 + 4 * lh - (first[j] ? 0 : p.n0);
-            orow[i][j] = m < p.M && nc0 + j * 32 < p.N ? (unsigned)(m * (first[j] ? p.n0 : n1) + c) * 4u : LEAN_OOB;
-        }
-    }
-    f32x4 ov[FM][FN][4];               // MASK: the mask of each output; else the bias of its channels
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-        if constexpr (MASK) {
-            const float* mk = first[j] ? p.mask0 : p.mask1;
-            const __amdgpu_buffer_rsrc_t r = epi_rsrc(mk, mk != nullptr);
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    ov[i][j][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, orow[i][j], 32 * q, 0));
-        } else {
-            const __amdgpu_buffer_rsrc_t r = epi_rsrc(p.bias, true);
-            const unsigned nb = nc0 + j * 32 < p.N ? (unsigned)(nc0 + j * 32 + 4 * lh) * 4u : LEAN_OOB;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                ov[0][j][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, nb, 32 * q, 0));
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-        const __amdgpu_buffer_rsrc_t rd = epi_rsrc(first[j] ? p.dst0 : p.dst1, true);
-        const bool has_mk = (first[j] ? p.mask0 : p.mask1) != nullptr;
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                if constexpr (!MASK) v += ov[0][j][q];
-                if (relu) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                if constexpr (MASK) {
-                    if (has_mk) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (!(ov[i][j][q][e] > 0.f)) v[e] = 0.f;
-                    }
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rd, orow[i][j], 32 * q, 0);
-            }
-    }
-}
-
-// The ConvTranspose2d 2x2 / s2 forward's epilogue (SHUFFLE2 without a crop: column n = ij * co + c
-// goes to pixel (2ho + i, 2wo + j) of the 2H x 2W grid, + bias[c]) in the same batched form: every
-// bias load before the first store.  co % 32 == 0, so a 32-column fragment lies in one (i, j).
-template <int FM, int FN>
-__device__ __forceinline__ void epilogue_batched_shuf(const IgemmParams& p, f32x16 (&acc)[FM][FN], int m0, int nc0,
-                                                      int lr, int lh) {
-    const bool relu = p.flags & PU_EPI_RELU;
-    const int co = p.N >> 2;
-    unsigned orow[FM][FN];
-    int cj[FN];
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-        const int nj = nc0 + j * 32;
-        const int ij = nj < p.N ? nj / co : 0;
-        cj[j] = nj - ij * co + 4 * lh;
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-            const int m = m0 + i * 32 + lr;
-            unsigned o = LEAN_OOB;
-            if (m < p.M && nj < p.N) {
-                const int t2 = fdiv(m, p.dWo);
-                const int wo = m - t2 * p.Wo;
-                const int bb = fdiv(t2, p.dHo);
-                const int ho = t2 - bb * p.Ho;
-                const int pix = (bb * p.shuf_h + 2 * ho + (ij >> 1)) * p.shuf_w + 2 * wo + (ij & 1);
-                o = (unsigned)(pix * co + cj[j]) * 4u;
-            }
-            orow[i][j] = o;
-        }
-    }
-    f32x4 bv[FN][4];
-    const __amdgpu_buffer_rsrc_t rb = epi_rsrc(p.bias, true);
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            bv[j][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                rb, nc0 + j * 32 < p.N ? (unsigned)cj[j] * 4u : LEAN_OOB, 32 * q, 0));
-    const __amdgpu_buffer_rsrc_t rd = epi_rsrc(p.dst0, true);
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                v += bv[j][q];
-                if (relu) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rd, orow[i][j], 32 * q, 0);
-            }
-}
-
+// BATCH: the kernel offers the batched forms (conv_common.h): x6 and x6 lean do, dma and the loader
+// kernels do not.  The conditions are igemm_bf16.hip's epi_batch_b_ok / epi_shuf_b_ok plus the two
+// fields only IgemmParams has (vec_epi, cscale).
 template <int BM, int BN, int WM, int WN, bool BATCH = false>
 __device__ __forceinline__ void epilogue(const IgemmParams& p, f32x16 (&acc)[BM / WM / 32][BN / WN / 32], int m_blk,
                                          int n_blk, int wm, int wn, int lr, int lh) {
@@ -457,8 +320,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
 // 16-byte chunk kc of row r is stored at position kc ^ ((r >> 2) & 3) (XOR swizzle on the global
 // SOURCE address, same XOR on the ds_read_b128 address) so the MFMA operand reads are
 // conflict-free.  NBUF-deep ring with a counted s_waitcnt vmcnt and a raw s_barrier per stage.
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
 __device__ __attribute__((aligned(16))) float g_zero16[4];
 
 template <int BM, int BN, int WM, int WN, int NBUF>
@@ -613,24 +474,7 @@ __global__ __launch_bounds__(256) void igemm_dma_kernel(const IgemmParams p) {
         epilogue<BM, BN, WM, WN>(p, acc, m_blk, n_blk, wm, wn, lr, lh);
         return;
     }
-    // split-K: raw partial tile -> part[kz][m][n] (float4 over 4 consecutive n; N % 4 == 0)
-    float* part = p.part + (long long)kz * p.M * p.N;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-        const int m = m_blk + wm * (BM / WM) + i * 32 + lr;
-        if (m >= p.M) continue;
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int n = n_blk + wn * (BN / WN) + j * 32 + 8 * q + 4 * lh;
-                if (n >= p.N) continue;
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                *reinterpret_cast<f32x4*>(part + (long long)m * p.N + n) = v;
-            }
-    }
+    PU_STORE_PARTIAL_TILE(p, acc, kz, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
 }
 
 // ------------------------------------------------------------- fp32 GEMM as 6 bf16 MFMA products
@@ -826,23 +670,7 @@ __global__ __launch_bounds__(NW * 64) void igemm_x6_kernel(const IgemmParams p) 
         epilogue<BM, BN, WM, WN, true>(p, acc, m_blk, n_blk, wm, wn, lr, lh);
         return;
     }
-    float* part = p.part + (long long)kz * p.M * p.N;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-        const int m = m_blk + wm * (BM / WM) + i * 32 + lr;
-        if (m >= p.M) continue;
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int n = n_blk + wn * (BN / WN) + j * 32 + 8 * q + 4 * lh;
-                if (n >= p.N) continue;
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                *reinterpret_cast<f32x4*>(part + (long long)m * p.N + n) = v;
-            }
-    }
+    PU_STORE_PARTIAL_TILE(p, acc, kz, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
 }
 
 // ---------------------------------------------------------------- lean 6-product kernel
@@ -1033,23 +861,7 @@ __global__ __launch_bounds__(NW * 64) void igemm_x6_lean_kernel(const IgemmParam
         epilogue<BM, BN, WM, WN, true>(p, acc, m_blk, n_blk, wm, wn, lr, lh);
         return;
     }
-    float* part = p.part + (long long)kz * p.M * p.N;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-        const int m = m_blk + wm * (BM / WM) + i * 32 + lr;
-        if (m >= p.M) continue;
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int n = n_blk + wn * (BN / WN) + j * 32 + 8 * q + 4 * lh;
-                if (n >= p.N) continue;
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                *reinterpret_cast<f32x4*>(part + (long long)m * p.N + n) = v;
-            }
-    }
+    PU_STORE_PARTIAL_TILE(p, acc, kz, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
 }
 
 // packed fp32 weight [n][k_pad] -> [k_pad/16][q][n][8] bf16 planes, q = plane*2 + (k%16)/8,
@@ -1073,19 +885,8 @@ __global__ void split_weight6_kernel(const float* __restrict__ w, __bf16* __rest
     }
 }
 
-// split-K second pass: sum the partial tiles in split order (deterministic) + the fused epilogue
-__global__ __launch_bounds__(256) void igemm_splitk_epilogue_kernel(const IgemmParams p) {
-    const int nq = p.N >> 2;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)p.M * nq) return;
-    const int m = (int)(idx / nq);
-    const int n = (int)(idx - (long long)m * nq) * 4;
-    const long long mn = (long long)p.M * p.N;
-    const float* src = p.part + (long long)m * p.N + n;
-    f32x4 v = *reinterpret_cast<const f32x4*>(src);
-    for (int z = 1; z < p.ksplit; ++z) v += *reinterpret_cast<const f32x4*>(src + z * mn);
-    epi_store4(p, epi_row(p, m), n, v);
-}
+// split-K second pass (conv_common.h splitk_finish)
+__global__ __launch_bounds__(256) void igemm_splitk_epilogue_kernel(const IgemmParams p) { splitk_finish(p); }
 
 // ---------------------------------------------------------------- small-channel direct conv
 // For 3x3/s1/p1 convolutions with C <= 16 input and N <= 16 output channels (the 8/16-channel
@@ -1435,16 +1236,9 @@ static bool uses_x6(const pu_conv_args* a) {
     return a->weight6 && choose_mode(a->c0, a->c1) == LOAD_CHUNK16 && !small_conv_ok(a);
 }
 
-// What one call runs: the kernel, the tile and loader mode pu_conv_igemm_tile reports, its K split
-// and the scratch the planned split needs.  pu_conv_igemm launches the plan, the two queries report
-// it.
+// The kernels a plan (conv_common.h ConvPlan) can name; its mode is what pu_conv_igemm_tile reports:
+// 0 chunk16, 1 vec4, 2 scalar, 3 direct, 4 x6, 5 stem, 6 wino, 7 x6s.
 enum { CK_STEM, CK_1X1, CK_SMALLX6, CK_DIRECT, CK_WINO, CK_X6_LEAN, CK_X6, CK_DMA, CK_LOADER };
-struct ConvPlan {
-    int kind, bm, bn;
-    int mode;               // 0 chunk16, 1 vec4, 2 scalar, 3 direct, 4 x6, 5 stem, 6 wino, 7 x6s
-    int ksplit, t_per;      // the split this call runs: 1 without the scratch the plan asks for
-    size_t ws_bytes;        // fp32 partial tiles of the planned split (0: the plan does not split)
-};
 
 // The dispatch ladder: stem, 1x1 small, smallx6, small-channel direct, Winograd, then the tiled
 // kernels (x6 lean, x6, DMA, loader modes) on plan_tiles' tile.  Reads a as it is: the launcher
@@ -1506,50 +1300,14 @@ static ConvPlan plan_conv(const pu_conv_args* a, long long M) {
 using namespace pu;
 
 extern "C" int pu_conv_igemm(const pu_conv_args* a, void* stream) {
-    PU_REQUIRE(a != nullptr, "pu_conv_igemm: null args");
-    PU_REQUIRE(a->batch > 0 && a->in_h > 0 && a->in_w > 0 && a->out_h > 0 && a->out_w > 0,
-               "pu_conv_igemm: bad grid %dx%dx%d -> %dx%d", a->batch, a->in_h, a->in_w, a->out_h, a->out_w);
-    PU_REQUIRE(a->kh > 0 && a->kw > 0 && a->stride > 0 && a->pad >= 0, "pu_conv_igemm: bad taps");
-    PU_REQUIRE(a->kh * a->kw <= 32, "pu_conv_igemm: at most 32 taps");
-    PU_REQUIRE(a->src0 && a->c0 > 0, "pu_conv_igemm: src0 missing");
-    PU_REQUIRE(a->c1 == 0 || a->src1, "pu_conv_igemm: src1 missing for c1=%d", a->c1);
-    PU_REQUIRE(a->weight && a->dst0 && a->n > 0, "pu_conv_igemm: weight/dst0/n");
+    long long M;
+    if (const int st = conv_check_args(a, "pu_conv_igemm", IG_BK, &M)) return st;
     const int C = a->c0 + a->c1;
-    const int K = a->kh * a->kw * C;
-    PU_REQUIRE(a->k_pad >= K && a->k_pad % IG_BK == 0, "pu_conv_igemm: k_pad %d must be >= %d and a multiple of 16", a->k_pad, K);
     const bool shuffle = a->flags & PU_EPI_SHUFFLE2;
-    if (a->flags & PU_EPI_RESID) {
-        PU_REQUIRE(a->resid && !shuffle && (a->n0 == a->n), "pu_conv_igemm: RESID needs resid, a single destination, no SHUFFLE2");
-    }
-    if (shuffle) {
-        PU_REQUIRE(a->n % 4 == 0, "pu_conv_igemm: SHUFFLE2 needs n %% 4 == 0");
-        PU_REQUIRE(a->shuf_off >= 0 && a->shuf_h >= 0 && a->shuf_w >= 0, "pu_conv_igemm: shuffle geometry");
-    } else {
-        PU_REQUIRE(a->n0 > 0 && a->n0 <= a->n, "pu_conv_igemm: n0 %d out of range", a->n0);
-        PU_REQUIRE(a->n0 == a->n || a->dst1, "pu_conv_igemm: dst1 missing");
-    }
-    const long long M = (long long)a->batch * a->out_h * a->out_w;
-    PU_REQUIRE(M < (1LL << 31) && (long long)a->batch * a->in_h * a->in_w < (1LL << 31), "pu_conv_igemm: too many pixels");
 
     IgemmParams p;
-    p.M = (int)M; p.N = a->n; p.K = K; p.k_pad = a->k_pad;
-    p.Hi = a->in_h; p.Wi = a->in_w; p.Ho = a->out_h; p.Wo = a->out_w;
-    p.kh = a->kh; p.kw = a->kw; p.stride = a->stride; p.pad = a->pad;
-    p.C = C; p.c0 = a->c0; p.c1 = a->c1;
-    p.src0 = a->src0; p.src1 = a->src1; p.wt = a->weight; p.bias = a->bias;
-    p.dst0 = a->dst0; p.dst1 = a->dst1; p.mask0 = a->mask0; p.mask1 = a->mask1;
-    p.n0 = shuffle ? a->n : a->n0; p.flags = a->flags;
-    p.resid = (a->flags & PU_EPI_RESID) ? a->resid : nullptr;
-    p.shuf_h = a->shuf_h ? a->shuf_h : 2 * a->out_h;
-    p.shuf_w = a->shuf_w ? a->shuf_w : 2 * a->out_w;
-    p.shuf_off = a->shuf_off;
-    p.dWo = make_fastdiv(a->out_w); p.dHo = make_fastdiv(a->out_h);
-    p.dC = make_fastdiv(C); p.dKw = make_fastdiv(a->kw); p.dCo = make_fastdiv(shuffle ? a->n / 4 : 1);
-    p.taps = a->kh * a->kw;
-    p.dTaps = make_fastdiv(p.taps);
-    p.cgroup = a->cgroup;
+    conv_fill_params(a, M, &p);
     p.vec_epi = vec_epilogue(a);
-    p.in_pix = a->batch * a->in_h * a->in_w;
     p.cscale = a->chan_scale;
     p.cs_ld = a->chan_scale_ld ? a->chan_scale_ld : (shuffle ? a->n / 4 : a->n);
     p.dHW = make_fastdiv(a->out_h * a->out_w);

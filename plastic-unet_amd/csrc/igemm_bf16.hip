@@ -3,120 +3,32 @@
 // v_mfma_f32_32x32x16_bf16 accumulates in fp32; bias is fp32; outputs are rounded to bf16 once, in
 // the epilogue.
 //
-// Same machinery as igemm.hip's direct-to-LDS kernel, byte for byte: a stage is 64-byte LDS rows
+// Shared with igemm.hip by inclusion (conv_common.h): the parameter block (ConvParams<__bf16> as
+// IgemmBf16Params), the epilogue family (epi_row / epi_store4 and the batched mask / bias / shuffle
+// forms; which form a launch takes is epi_batch_b_ok / epi_shuf_b_ok below), the split-K
+// partial-tile store and finish, ConvPlan, and
+// the host's shared argument rules and parameter fill.  This file holds the bf16 main loops and
+// loaders, the row-stream kernel's own preloaded epilogue, the bf16 plan ladder and its checks.
+//
+// The tile kernel is the machinery of igemm.hip's direct-to-LDS kernel: a stage is 64-byte LDS rows
 // filled by global_load_lds_dwordx4 with the XOR swizzle kc ^ ((r>>2)&3), a 3-deep ring, counted
 // vmcnt + raw barrier, branch-free loader.  A 64-byte row now holds 32 bf16 k-values (BK = 32) and
 // a lane's 16-byte chunk is exactly one 32x32x16 operand fragment (8 consecutive k of its row:
 // A[row l&31][k = 8h + j], B[k = 8h + j][col l&31]), so each (i, j) sub-tile takes 2 MFMAs per
 // stage.  Weights are the A operand, pixels the B operand: each lane owns 4 consecutive output
 // channels of one pixel, stored as 8 bytes.
-#include "common.h"
+#include "conv_common.h"
 
 namespace pu {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK16 = 32;   // k per stage (64 B of bf16)
 
-struct IgemmBf16Params {
-    int M, N, K, k_pad;
-    int Hi, Wi, Ho, Wo, kh, kw, stride, pad;
-    int C, c0, c1;
-    const __bf16* src0;
-    const __bf16* src1;
-    const __bf16* wt;
-    const float* bias;
-    __bf16* dst0;
-    __bf16* dst1;
-    const __bf16* mask0;
-    const __bf16* mask1;
-    const __bf16* resid;
-    int n0, flags;
-    int cgroup, taps, gn;
-    int ksplit, t_per;
-    float* part;
-    int shuf_h, shuf_w, shuf_off;
-    FastDiv dWo, dHo, dC, dKw, dCo, dTaps;
-    int in_pix;             // batch * Hi * Wi (the lean kernel's buffer extent)
-};
-
-struct EpiRowB {
-    long long pix;
-    int oh0, ow0;
-};
-
-__device__ __forceinline__ EpiRowB epi_row_b(const IgemmBf16Params& p, int m) {
-    if (!(p.flags & PU_EPI_SHUFFLE2)) return {m, 0, 0};
-    const int t2 = fdiv(m, p.dWo);
-    const int wo = m - t2 * p.Wo;
-    const int bb = fdiv(t2, p.dHo);
-    const int ho = t2 - bb * p.Ho;
-    return {(long long)bb * p.shuf_h, 2 * ho - p.shuf_off, 2 * wo - p.shuf_off};
-}
-
-__device__ __forceinline__ f32x4 ld4(const __bf16* p) {
-    const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
-    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
-
-// epilogue of output channels n..n+3 (n % 4 == 0, N % 4 == 0, n0 % 4 == 0) of row r
-__device__ __forceinline__ void epi_store4_b(const IgemmBf16Params& p, const EpiRowB& r, int n, f32x4 v) {
-    __bf16* dst;
-    const __bf16* msk;
-    long long off;
-    int nb;
-    if (p.flags & PU_EPI_SHUFFLE2) {
-        const int co = p.N >> 2;
-        const int ij = fdiv(n, p.dCo);
-        nb = n - ij * co;
-        const int oh = r.oh0 + (ij >> 1), ow = r.ow0 + (ij & 1);
-        if ((unsigned)oh >= (unsigned)p.shuf_h || (unsigned)ow >= (unsigned)p.shuf_w) return;
-        off = ((r.pix + oh) * p.shuf_w + ow) * co + nb;
-        dst = p.dst0; msk = p.mask0;
-    } else if (n < p.n0) {
-        off = r.pix * p.n0 + n;
-        dst = p.dst0; msk = p.mask0; nb = n;
-    } else {
-        off = r.pix * (p.N - p.n0) + (n - p.n0);
-        dst = p.dst1; msk = p.mask1; nb = n;
-    }
-    if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + nb);
-    if (p.resid) v += ld4(p.resid + off);
-    if (p.flags & PU_EPI_RELU) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-    }
-    if (msk) {
-        const f32x4 mv = ld4(msk + off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) if (!(mv[e] > 0.f)) v[e] = 0.f;
-    }
-    if (p.flags & PU_EPI_ACCUM) v += ld4(dst + off);
-    bf16x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (__bf16)v[e];
-    *reinterpret_cast<bf16x4*>(dst + off) = o;
-}
-
-// The two common epilogue forms - bias (+ReLU), the forward, or masks (+ReLU), the data gradient -
-// for an [NI][NJ] grid of 32 x 32 accumulator fragments, with every operand load issued before the
-// first store: gfx9's vmcnt counts stores too, so epi_store4_b's load-then-store per output made
-// each output wait out the previous stores' round trips (in the persistent halo kernel, right
-// before the next tile's first group).  Buffer descriptors with 32-bit offsets, wave-uniform per
-// 32-column fragment (n0 % 32 == 0); lanes past M / N load zeros and drop their stores.  Same
-// operations and rounding as epi_store4_b.  epi_batch_b_ok: the launch takes this form.
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t epi_rsrc_b(const void* base, bool on) {
-    const unsigned long long b = (unsigned long long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    void* ub = (void*)(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(ub, 0, on ? 0x7fffffff : 0, 0x00020000);
-}
-
+// The batched epilogue form (conv_common.h) a launch takes: the lean and halo kernels offer the mask
+// and bias forms, the tile kernel the shuffle form.  The conditions of igemm.hip's epilogue<>, minus
+// the fields only IgemmParams has.
 __device__ __forceinline__ int epi_batch_b_ok(const IgemmBf16Params& p) {
     if ((p.flags & (PU_EPI_SHUFFLE2 | PU_EPI_ACCUM)) || p.resid || p.n0 % 32 || p.N % 32 ||
         (long long)p.M * p.N >= (1LL << 29))
@@ -124,139 +36,10 @@ __device__ __forceinline__ int epi_batch_b_ok(const IgemmBf16Params& p) {
     const bool mk = p.mask0 || p.mask1;
     return mk && !p.bias ? 1 : (!mk && p.bias ? 2 : 0);     // 1 masks, 2 bias
 }
-
-template <bool MASK, int NI, int NJ>
-__device__ __forceinline__ void epilogue_batched_b(const IgemmBf16Params& p, f32x16 (&acc)[NI][NJ], int m0, int nc0,
-                                                   int lr, int lh) {
-    const bool relu = p.flags & PU_EPI_RELU;
-    const int n1 = p.N - p.n0;
-    unsigned orow[NI][NJ];             // byte offset of (row m, fragment column 0), LEAN_OOB past M / N
-    bool first[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) first[j] = nc0 + j * 32 < p.n0;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int m = m0 + i * 32 + lr;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int c = nc0 + j * 32 + 4 * lh - (first[j] ? 0 : p.n0);
-            orow[i][j] = m < p.M && nc0 + j * 32 < p.N ? (unsigned)(m * (first[j] ? p.n0 : n1) + c) * 2u : LEAN_OOB;
-        }
-    }
-    u32x2_t mv[NI][NJ][4];             // MASK: 4 bf16 mask values per output
-    f32x4 bv[NJ][4];                   // !MASK: the bias of the output's channels
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        if constexpr (MASK) {
-            const __bf16* mk = first[j] ? p.mask0 : p.mask1;
-            const __amdgpu_buffer_rsrc_t r = epi_rsrc_b(mk, mk != nullptr);
-#pragma unroll
-            for (int i = 0; i < NI; ++i)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) mv[i][j][q] = __builtin_amdgcn_raw_buffer_load_b64(r, orow[i][j], 16 * q, 0);
-        } else {
-            const __amdgpu_buffer_rsrc_t r = epi_rsrc_b(p.bias, true);
-            const unsigned nb = nc0 + j * 32 < p.N ? (unsigned)(nc0 + j * 32 + 4 * lh) * 4u : LEAN_OOB;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                bv[j][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, nb, 32 * q, 0));
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const __amdgpu_buffer_rsrc_t rd = epi_rsrc_b(first[j] ? p.dst0 : p.dst1, true);
-        const bool has_mk = (first[j] ? p.mask0 : p.mask1) != nullptr;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                if constexpr (!MASK) v += bv[j][q];
-                if (relu) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                if constexpr (MASK) {
-                    if (has_mk) {
-                        const bf16x4 mb = __builtin_bit_cast(bf16x4, mv[i][j][q]);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (!((float)mb[e] > 0.f)) v[e] = 0.f;
-                    }
-                }
-                bf16x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (__bf16)v[e];
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, o), rd, orow[i][j], 16 * q, 0);
-            }
-    }
-}
-
-// The ConvTranspose2d 2x2 / s2 forward (SHUFFLE2, no crop, bias, co % 32 == 0) in the batched form:
-// every bias load before the first store (the per-output epi_store4_b waited out each previous
-// store's round trip before its bias load).  Same operations and rounding as epi_store4_b.
 __device__ __forceinline__ bool epi_shuf_b_ok(const IgemmBf16Params& p) {
     return (p.flags & PU_EPI_SHUFFLE2) && !(p.flags & PU_EPI_ACCUM) && !p.resid && p.bias && !p.mask0 &&
            p.shuf_off == 0 && p.shuf_h == 2 * p.Ho && p.shuf_w == 2 * p.Wo && (p.N / 4) % 32 == 0 && p.N % 128 == 0 &&
            (long long)p.M * p.N < (1LL << 29);
-}
-
-template <int NI, int NJ>
-__device__ __forceinline__ void epilogue_batched_shuf_b(const IgemmBf16Params& p, f32x16 (&acc)[NI][NJ], int m0,
-                                                        int nc0, int lr, int lh) {
-    const bool relu = p.flags & PU_EPI_RELU;
-    const int co = p.N >> 2;
-    unsigned orow[NI][NJ];
-    int cj[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int nj = nc0 + j * 32;
-        const int ij = nj < p.N ? nj / co : 0;
-        cj[j] = nj - ij * co + 4 * lh;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int m = m0 + i * 32 + lr;
-            unsigned o = LEAN_OOB;
-            if (m < p.M && nj < p.N) {
-                const int t2 = fdiv(m, p.dWo);
-                const int wo = m - t2 * p.Wo;
-                const int bb = fdiv(t2, p.dHo);
-                const int ho = t2 - bb * p.Ho;
-                const int pix = (bb * p.shuf_h + 2 * ho + (ij >> 1)) * p.shuf_w + 2 * wo + (ij & 1);
-                o = (unsigned)(pix * co + cj[j]) * 2u;
-            }
-            orow[i][j] = o;
-        }
-    }
-    f32x4 bv[NJ][4];
-    const __amdgpu_buffer_rsrc_t rb = epi_rsrc_b(p.bias, true);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            bv[j][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                rb, nc0 + j * 32 < p.N ? (unsigned)cj[j] * 4u : LEAN_OOB, 32 * q, 0));
-    const __amdgpu_buffer_rsrc_t rd = epi_rsrc_b(p.dst0, true);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                v += bv[j][q];
-                if (relu) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                bf16x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (__bf16)v[e];
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, o), rd, orow[i][j], 16 * q, 0);
-            }
 }
 
 // s_waitcnt vmcnt(base + extra) for a run-time extra in {0, 2, ..., 62 - base} (wave-uniform);
@@ -274,8 +57,6 @@ __device__ __forceinline__ void wait_vm_plus(int extra) {
     }
 }
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
 __device__ __attribute__((aligned(16))) __bf16 g_zero_b16[8];
 
 template <int BM, int BN, int WM, int WN, int NBUF>
@@ -415,34 +196,18 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(const IgemmBf16Params p
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     if (p.ksplit > 1) {
-        float* part = p.part + (long long)kz * p.M * p.N;
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-            const int m = m_blk + wm * (BM / WM) + i * 32 + lr;
-            if (m >= p.M) continue;
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int n = n_blk + wn * (BN / WN) + j * 32 + 8 * q + 4 * lh;
-                    if (n >= p.N) continue;
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                    *reinterpret_cast<f32x4*>(part + (long long)m * p.N + n) = v;
-                }
-        }
+        PU_STORE_PARTIAL_TILE(p, acc, kz, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
         return;
     }
     if (epi_shuf_b_ok(p)) {
-        epilogue_batched_shuf_b(p, acc, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
+        epilogue_batched_shuf(p, acc, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
         return;
     }
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
         const int m = m_blk + wm * (BM / WM) + i * 32 + lr;
         if (m >= p.M) continue;
-        const EpiRowB er = epi_row_b(p, m);
+        const EpiRow er = epi_row(p, m);
 #pragma unroll
         for (int j = 0; j < FN; ++j)
 #pragma unroll
@@ -452,7 +217,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(const IgemmBf16Params p
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                epi_store4_b(p, er, n, v);
+                epi_store4(p, er, n, v);
             }
     }
 }
@@ -610,35 +375,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     if (p.ksplit > 1) {
-        float* part = p.part + (long long)kz * p.M * p.N;
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-            const int m = m_blk + wm * (BM / WM) + i * 32 + lr;
-            if (m >= p.M) continue;
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int n = n_blk + wn * (BN / WN) + j * 32 + 8 * q + 4 * lh;
-                    if (n >= p.N) continue;
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                    *reinterpret_cast<f32x4*>(part + (long long)m * p.N + n) = v;
-                }
-        }
+        PU_STORE_PARTIAL_TILE(p, acc, kz, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
         return;
     }
     if (const int eb = epi_batch_b_ok(p)) {
-        if (eb == 1) epilogue_batched_b<true>(p, acc, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
-        else epilogue_batched_b<false>(p, acc, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
+        if (eb == 1) epilogue_batched<true>(p, acc, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
+        else epilogue_batched<false>(p, acc, m_blk + wm * (BM / WM), n_blk + wn * (BN / WN), lr, lh);
         return;
     }
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
         const int m = m_blk + wm * (BM / WM) + i * 32 + lr;
         if (m >= p.M) continue;
-        const EpiRowB er = epi_row_b(p, m);
+        const EpiRow er = epi_row(p, m);
 #pragma unroll
         for (int j = 0; j < FN; ++j)
 #pragma unroll
@@ -648,7 +397,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) vo
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                epi_store4_b(p, er, n, v);
+                epi_store4(p, er, n, v);
             }
     }
 }
@@ -813,14 +562,14 @@ __global__ __launch_bounds__(HB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
         }
         const int eb = epi_batch_b_ok(p);
         if (eb == 1) {
-            epilogue_batched_b<true>(p, acc, m_blk + p0, n_blk, lr, lh);
+            epilogue_batched<true>(p, acc, m_blk + p0, n_blk, lr, lh);
         } else if (eb == 2) {
-            epilogue_batched_b<false>(p, acc, m_blk + p0, n_blk, lr, lh);
+            epilogue_batched<false>(p, acc, m_blk + p0, n_blk, lr, lh);
         } else {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int m = m_blk + p0 + i * 32 + lr;
-                const EpiRowB er = epi_row_b(p, m);
+                const EpiRow er = epi_row(p, m);
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -829,7 +578,7 @@ __global__ __launch_bounds__(HB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
                         f32x4 v;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-                        epi_store4_b(p, er, n, v);
+                        epi_store4(p, er, n, v);
                     }
             }
         }
@@ -1026,18 +775,8 @@ __global__ __launch_bounds__(256) void igemm_bf16_rows_kernel(const IgemmBf16Par
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the trailing (empty) row loads drain
 }
 
-__global__ __launch_bounds__(256) void igemm_bf16_splitk_epilogue_kernel(const IgemmBf16Params p) {
-    const int nq = p.N >> 2;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)p.M * nq) return;
-    const int m = (int)(idx / nq);
-    const int n = (int)(idx - (long long)m * nq) * 4;
-    const long long mn = (long long)p.M * p.N;
-    const float* src = p.part + (long long)m * p.N + n;
-    f32x4 v = *reinterpret_cast<const f32x4*>(src);
-    for (int z = 1; z < p.ksplit; ++z) v += *reinterpret_cast<const f32x4*>(src + z * mn);
-    epi_store4_b(p, epi_row_b(p, m), n, v);
-}
+// split-K second pass (conv_common.h splitk_finish)
+__global__ __launch_bounds__(256) void igemm_bf16_splitk_epilogue_kernel(const IgemmBf16Params p) { splitk_finish(p); }
 
 // the halo kernel: 3x3 / s1 / p1 same-size, width 32 / 64 / 128, whole 256-pixel row blocks,
 // 32-channel groups, 64-channel output tiles, plain (non-SHUFFLE2) epilogue
@@ -1050,17 +789,6 @@ static bool halo_ok_b(const pu_conv_args* a) {
     if ((long long)a->batch * a->in_h * a->in_w * (a->c0 > a->c1 ? a->c0 : a->c1) >= (1LL << 31)) return false;
     if ((long long)a->k_pad * a->n >= (1LL << 31)) return false;
     return true;
-}
-
-static int device_cus_b() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev]) {
-        int n = 0;
-        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8) ? n : 256;
-    }
-    return cus[dev];
 }
 
 // the row-stream kernel: the halo kernel's 3x3 / s1 / p1 shapes restricted to width 128, one
@@ -1085,19 +813,12 @@ static bool lean_ok_b(const pu_conv_args* a) {
     return true;
 }
 
-// What one call runs: the kernel (the kind pu_conv_igemm_bf16_tile reports), its tile, its K split
-// and the scratch the planned split needs.  pu_conv_igemm_bf16 launches the plan, the two queries
-// report it.
+// The kernels a plan (conv_common.h ConvPlan) can name: the kind pu_conv_igemm_bf16_tile reports.
 enum { B16_TILE = 0, B16_LEAN = 1, B16_HALO = 2, B16_ROWS = 3 };
-struct Bf16Plan {
-    int kind, bm, bn;
-    int ksplit, t_per;      // the split this call runs: 1 without the scratch the plan asks for
-    size_t ws_bytes;        // fp32 partial tiles of the planned split (0: the plan does not split)
-};
 
 // lean tiles: 256 x 128 (N > 64) or 256 x 64, 4 waves, ~2 resident blocks per CU (72 / 61 KB of
 // LDS); small pixel grids split K on group boundaries until ~2 blocks per CU
-static void plan_lean_b(const pu_conv_args* a, long long M, Bf16Plan* pl) {
+static void plan_lean_b(const pu_conv_args* a, long long M, ConvPlan* pl) {
     const int T = a->k_pad / BK16;
     const int target = 512;
     pl->bm = 256;
@@ -1123,8 +844,9 @@ static void plan_lean_b(const pu_conv_args* a, long long M, Bf16Plan* pl) {
 }
 
 // The dispatch ladder: rows, halo, lean, tiled.  a has passed setup_bf16.
-static Bf16Plan plan_conv_b(const pu_conv_args* a, long long M) {
-    Bf16Plan pl;
+static ConvPlan plan_conv_b(const pu_conv_args* a, long long M) {
+    ConvPlan pl;
+    pl.mode = 0;
     pl.ksplit = 1;
     pl.t_per = a->k_pad / BK16;
     pl.ws_bytes = 0;
@@ -1158,51 +880,23 @@ static Bf16Plan plan_conv_b(const pu_conv_args* a, long long M) {
     return pl;
 }
 
-static int setup_bf16(const pu_conv_args* a, IgemmBf16Params* pp, long long* Mout) {
-    PU_REQUIRE(a != nullptr, "pu_conv_igemm_bf16: null args");
-    PU_REQUIRE(a->batch > 0 && a->in_h > 0 && a->in_w > 0 && a->out_h > 0 && a->out_w > 0, "pu_conv_igemm_bf16: bad grid");
-    PU_REQUIRE(a->kh > 0 && a->kw > 0 && a->stride > 0 && a->pad >= 0 && a->kh * a->kw <= 32, "pu_conv_igemm_bf16: bad taps");
-    PU_REQUIRE(a->src0 && a->weight && a->dst0 && a->n > 0, "pu_conv_igemm_bf16: operands");
+// the shared argument rules, then this entry's own; fills every field of *pp but the plan's
+static int setup_bf16(const pu_conv_args* a, IgemmBf16Params* pp, long long* M) {
+    if (const int st = conv_check_args(a, "pu_conv_igemm_bf16", BK16, M)) return st;
     PU_REQUIRE(a->chan_scale == nullptr, "pu_conv_igemm_bf16: chan_scale is an fp32-path epilogue");
     PU_REQUIRE(!(a->flags & PU_EPI_OUT_BF16), "pu_conv_igemm_bf16: PU_EPI_OUT_BF16 is pu_conv_igemm's stem flag");
-    PU_REQUIRE(a->c0 % 32 == 0 && a->c1 % 32 == 0 && a->c0 > 0 && (a->c1 == 0 || a->src1),
+    PU_REQUIRE(a->c0 % 32 == 0 && a->c1 % 32 == 0,
                "pu_conv_igemm_bf16: channel counts (%d, %d) must be multiples of 32", a->c0, a->c1);
     PU_REQUIRE(a->cgroup == 0 || a->cgroup == 32, "pu_conv_igemm_bf16: cgroup must be 0 or 32");
-    const int C = a->c0 + a->c1;
-    const int K = a->kh * a->kw * C;
-    PU_REQUIRE(a->k_pad >= K && a->k_pad % BK16 == 0, "pu_conv_igemm_bf16: k_pad %d (K %d) must be a multiple of 32", a->k_pad, K);
     const bool shuffle = a->flags & PU_EPI_SHUFFLE2;
     const int n0 = shuffle ? a->n : a->n0;
     PU_REQUIRE(a->n % 4 == 0 && n0 % 4 == 0 && (!shuffle || (a->n / 4) % 4 == 0), "pu_conv_igemm_bf16: channel alignment");
-    PU_REQUIRE(shuffle || (n0 > 0 && n0 <= a->n && (n0 == a->n || a->dst1)), "pu_conv_igemm_bf16: n0 / dst1");
-    PU_REQUIRE(!(a->flags & PU_EPI_RESID) || (a->resid && !shuffle && n0 == a->n), "pu_conv_igemm_bf16: RESID");
     const uintptr_t al = (uintptr_t)a->src0 | (uintptr_t)a->src1 | (uintptr_t)a->weight;
     PU_REQUIRE((al & 15) == 0, "pu_conv_igemm_bf16: sources / weight must be 16-byte aligned");
     const uintptr_t ae = (uintptr_t)a->dst0 | (uintptr_t)a->dst1 | (uintptr_t)a->mask0 | (uintptr_t)a->mask1 |
                          (uintptr_t)a->resid;
     PU_REQUIRE((ae & 7) == 0 && ((uintptr_t)a->bias & 15) == 0, "pu_conv_igemm_bf16: epilogue alignment");
-    const long long M = (long long)a->batch * a->out_h * a->out_w;
-    PU_REQUIRE(M < (1LL << 31), "pu_conv_igemm_bf16: too many pixels");
-    IgemmBf16Params& p = *pp;
-    p.M = (int)M; p.N = a->n; p.K = K; p.k_pad = a->k_pad;
-    p.Hi = a->in_h; p.Wi = a->in_w; p.Ho = a->out_h; p.Wo = a->out_w;
-    p.kh = a->kh; p.kw = a->kw; p.stride = a->stride; p.pad = a->pad;
-    p.C = C; p.c0 = a->c0; p.c1 = a->c1;
-    p.src0 = (const __bf16*)a->src0; p.src1 = (const __bf16*)a->src1; p.wt = (const __bf16*)a->weight;
-    p.bias = a->bias;
-    p.dst0 = (__bf16*)a->dst0; p.dst1 = (__bf16*)a->dst1;
-    p.mask0 = (const __bf16*)a->mask0; p.mask1 = (const __bf16*)a->mask1;
-    p.resid = (a->flags & PU_EPI_RESID) ? (const __bf16*)a->resid : nullptr;
-    p.n0 = n0; p.flags = a->flags;
-    p.cgroup = a->cgroup; p.taps = a->kh * a->kw;
-    p.shuf_h = a->shuf_h ? a->shuf_h : 2 * a->out_h;
-    p.shuf_w = a->shuf_w ? a->shuf_w : 2 * a->out_w;
-    p.shuf_off = a->shuf_off;
-    p.dWo = make_fastdiv(a->out_w); p.dHo = make_fastdiv(a->out_h);
-    p.dC = make_fastdiv(C); p.dKw = make_fastdiv(a->kw); p.dCo = make_fastdiv(shuffle ? a->n / 4 : 1);
-    p.dTaps = make_fastdiv(p.taps);
-    p.in_pix = a->batch * a->in_h * a->in_w;
-    *Mout = M;
+    conv_fill_params(a, *M, pp);
     return PU_OK;
 }
 
@@ -1222,7 +916,7 @@ extern "C" int pu_conv_igemm_bf16(const pu_conv_args* a, void* stream) {
     long long M;
     int st = setup_bf16(a, &p, &M);
     if (st != PU_OK) return st;
-    const Bf16Plan pl = plan_conv_b(a, M);
+    const ConvPlan pl = plan_conv_b(a, M);
     const int N = a->n;
     hipStream_t s = as_stream(stream);
     p.ksplit = pl.ksplit;
@@ -1241,7 +935,7 @@ extern "C" int pu_conv_igemm_bf16(const pu_conv_args* a, void* stream) {
             p.gn = N / HB_BN;
             const long long tiles = M / 256 * p.gn;
             const long long per_xcd = ceil_div(tiles, 8LL);
-            const int blocks_per_xcd = 2 * device_cus_b() / 8;   // 2 resident blocks per CU
+            const int blocks_per_xcd = 2 * device_cus() / 8;   // 2 resident blocks per CU
             const dim3 hgrid((unsigned)(8 * (per_xcd < blocks_per_xcd ? per_xcd : blocks_per_xcd)));
             if (a->out_w == 128) hipLaunchKernelGGL((igemm_bf16_halo_kernel<128>), hgrid, dim3(HB_NT), 0, s, p);
             else if (a->out_w == 64) hipLaunchKernelGGL((igemm_bf16_halo_kernel<64>), hgrid, dim3(HB_NT), 0, s, p);
@@ -1273,7 +967,7 @@ extern "C" int pu_conv_igemm_bf16_tile(const pu_conv_args* a, int* bm, int* bn, 
     long long M;
     int st = setup_bf16(a, &p, &M);
     if (st != PU_OK) return st;
-    const Bf16Plan pl = plan_conv_b(a, M);
+    const ConvPlan pl = plan_conv_b(a, M);
     *bm = pl.bm;
     *bn = pl.bn;
     if (ksplit) *ksplit = pl.ksplit;

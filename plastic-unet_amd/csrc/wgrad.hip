@@ -20,8 +20,6 @@
 
 namespace pu {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WG_BM = 16;  // pixel rows per LDS stage
 
@@ -240,8 +238,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
 // costs a whole extra tile whenever K or N is a multiple of the tile): the k-tile-0 blocks
 // (mode 1) or n-tile-0 blocks (mode 2) column-sum the staged P / Q image out of LDS on the VALU
 // and write the partial into slab column K / row N.
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
 __device__ __attribute__((aligned(16))) float g_wg_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 
 typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));

@@ -1,7 +1,7 @@
 """punet - host side of the MI355X plastic U-Net training path.
 
 Layers: ``_lib`` (ctypes binding of libplastic_unet.so), ``kernels`` (tensor wrappers, one per C-ABI
-entry point), ``trunk``/``head`` (autograd nodes that run only HIP kernels), ``optim`` (FusedAdam),
+entry point), ``packs`` (the packed conv operands and their cache), ``trunk``/``head`` (autograd nodes that run only HIP kernels), ``optim`` (FusedAdam),
 ``dp`` (data parallel over RCCL), ``engine`` (the batched training step used by train.py/bench.py).
 """
 from .head import BCELoss, bce_loss  # noqa: F401

@@ -9,6 +9,7 @@ import os
 import torch
 
 from . import _lib
+from . import packs     # PackedWeight, the operand pack_weight makes and igemm reads (packs calls back into here)
 from ._lib import (ConvArgs, WgradArgs, PlasticArgs, PlasticHeadArgs, PlasticBwdArgs, PlasticBwdTraceArgs, AdamTensor,
                    PackJob, WinoJob, check,
                    PU_EPI_RELU, PU_EPI_ACCUM, PU_EPI_SHUFFLE2, PU_EPI_RESID, PU_CONV_NO_HALO, PU_CONV_HALO_V1,
@@ -224,6 +225,16 @@ def cgroup_for(c0, c1=0):
     return 0
 
 
+_WINO_TAKES = {}    # call signature -> does pu_conv_igemm take the Winograd kernel for it
+
+
+def direct_call(weight):
+    """A call on this operand is about to take a direct kernel: its direct operand is repacked
+    first if the last repack skipped it, and refreshed with every repack from now on."""
+    if weight.take_direct():
+        pack_weights([weight], wino=False)
+
+
 def igemm(*, batch, in_hw, out_hw, k, stride, pad, src0, c0, weight, k_pad, n, dst0, n0=None,
           src1=None, c1=0, bias=None, dst1=None, mask0=None, mask1=None, relu=False, accum=False,
           shuffle=False, cgroup=0, resid=None, shuf=(0, 0, 0), chan_scale=None):
@@ -231,10 +242,13 @@ def igemm(*, batch, in_hw, out_hw, k, stride, pad, src0, c0, weight, k_pad, n, d
     resid: residual tensor added before ReLU/mask; shuf = (out_h, out_w, crop) of a SHUFFLE2 grid;
     chan_scale: [batch, ld] per-(image, column) factors applied after the mask (the Dropout2d scale
     of the tensor being produced; SHUFFLE2: per output channel).  A bf16 dst0 with fp32 operands
-    is the single-channel stem writing the bf16 trunk's first activation (PU_EPI_OUT_BF16)."""
+    is the single-channel stem writing the bf16 trunk's first activation (PU_EPI_OUT_BF16).
+    weight: the packs.PackedWeight of the parameter (pack_weight, or the trunk's Packs cache)."""
+    if not isinstance(weight, packs.PackedWeight):
+        raise TypeError("weight must be a PackedWeight (pack_weight or Packs.get), not %s" % type(weight).__name__)
     dt = _act_dtype(src0)
     out_bf16 = dt == torch.float32 and dst0 is not None and dst0.dtype == BF16
-    for t, nm in ((src0, "src0"), (src1, "src1"), (weight, "weight"), (dst0, "dst0"),
+    for t, nm in ((src0, "src0"), (src1, "src1"), (weight.direct, "weight"), (dst0, "dst0"),
                   (dst1, "dst1"), (mask0, "mask0"), (mask1, "mask1"), (resid, "resid")):
         _req(t, nm, BF16 if (out_bf16 and nm == "dst0") else dt)
     _req(bias, "bias")
@@ -243,27 +257,37 @@ def igemm(*, batch, in_hw, out_hw, k, stride, pad, src0, c0, weight, k_pad, n, d
         | (PU_EPI_RESID if resid is not None else 0) | _halo_flags() | (0 if _SMALLX6 else PU_CONV_NO_SMALLX6) \
         | (PU_EPI_OUT_BF16 if out_bf16 else 0)
     a = ConvArgs(batch, in_hw[0], in_hw[1], out_hw[0], out_hw[1], k, k, stride, pad,
-                 _p(src0), c0, _p(src1), c1, _p(weight), k_pad, cgroup, n, _p(bias),
+                 _p(src0), c0, _p(src1), c1, weight.data_ptr(), k_pad, cgroup, n, _p(bias),
                  _p(dst0), n if n0 is None else n0, _p(dst1), _p(mask0), _p(mask1), flags, None, 0,
                  _p(resid), shuf[0], shuf[1], shuf[2])
     if chan_scale is not None:
         if chan_scale.dim() != 2 or chan_scale.shape[0] != batch:
             raise RuntimeError("chan_scale must be [batch, channels]")
         a.chan_scale, a.chan_scale_ld = chan_scale.data_ptr(), chan_scale.shape[1]
-    w6 = getattr(weight, "_split6", None) if (dt != BF16 and _FP32_MATH == "split6") else None
-    wn = getattr(weight, "_wino", None) if (w6 is not None and _WINO) else None
+    w6 = weight.planes if (dt != BF16 and _FP32_MATH == "split6") else None
+    wn = weight.wino if (w6 is not None and _WINO) else None
     if w6 is not None:
         a.weight6 = w6.data_ptr()
     if wn is not None:
         a.wino = wn.data_ptr()
-        # the signature wino_ok reads: shapes, flags, which operands exist, their alignment
-        key = (batch, tuple(in_hw), tuple(out_hw), k, stride, pad, c0, c1, n, a.n0, k_pad, cgroup, flags,
-               tuple(None if t is None else t.data_ptr() % 16
-                     for t in (src0, src1, bias, dst0, dst1, mask0, mask1, resid, chan_scale, weight, w6, wn)))
-        _ensure_direct(a, weight, key)
-    elif getattr(weight, "_direct_ok", True) is False:     # a direct call (e.g. Winograd switched off)
-        _refresh_direct(weight)
     L = lib()
+    if weight.state != packs.KEPT:
+        # an operand that has only ever run on the Winograd kernel, so the last repack may have
+        # skipped its direct operand: does this call take the Winograd kernel too?
+        takes = False       # not without U (Winograd switched off, native fp32 math)
+        if wn is not None:
+            # the signature wino_ok reads: shapes, flags, which operands exist, their alignment
+            key = (batch, tuple(in_hw), tuple(out_hw), k, stride, pad, c0, c1, n, a.n0, k_pad, cgroup, flags,
+                   tuple(None if t is None else t.data_ptr() % 16 for t in
+                         (src0, src1, bias, dst0, dst1, mask0, mask1, resid, chan_scale, weight.direct, w6, wn)))
+            takes = _WINO_TAKES.get(key)
+            if takes is None:       # the library's answer, cached per signature
+                bm, bn, mode, ks = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+                check(L.pu_conv_igemm_tile(ctypes.byref(a), ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(mode),
+                                           ctypes.byref(ks)), "pu_conv_igemm_tile")
+                takes = _WINO_TAKES[key] = mode.value == 6
+        if not takes:
+            direct_call(weight)
     if dt == BF16:
         _igemm_bf16(L, a, batch, out_hw, k, c0, c1, n, dst0)
         return
@@ -368,93 +392,59 @@ def wgrad_kind(*, batch, hw, n, c0, c1=0, k=3):
     return qv.value
 
 
-def pack_weight(w, mode, k_pad, out=None, cgroup=0, dtype=torch.float32):
-    """Pack an fp32 parameter into a GEMM operand (fp32, or bf16 for the C3 kernels)."""
+def pack_weight(w, mode, k_pad, cgroup=0, dtype=torch.float32):
+    """Pack an fp32 parameter into its GEMM operands (fp32, or bf16 for the C3 kernels): a
+    packs.PackedWeight holding the direct operand and, for fp32 split6 math, its bf16 planes and
+    the Winograd operand of a 3x3 conv that qualifies."""
     _req(w, "w")
     d0, d1, kh, kw = w.shape
     taps = kh * kw
     rows = {0: d0, 1: d1, 2: taps * d1, 3: d0, 4: 4 * d1}[mode]
-    if out is None:
-        out = torch.empty(rows, k_pad, dtype=dtype, device=w.device)
-    fn = lib().pu_pack_weight_bf16 if out.dtype == BF16 else lib().pu_pack_weight
-    with _Rec("pack_weight", nbytes=4.0 * w.numel() + out.element_size() * out.numel()):
-        check(fn(w.data_ptr(), out.data_ptr(), mode, d0, d1, kh, kw, k_pad, cgroup, _stream()), "pu_pack_weight")
-    if out.dtype == torch.float32 and _FP32_MATH == "split6" and k_pad % 16 == 0:
-        out._split6 = split_weight6(out)      # travels with the packed operand (igemm picks it up)
-        # so does the Winograd operand of a 3x3 conv - only while Winograd dispatch is on, so a
-        # PU_WINO=0 run neither holds nor refreshes U (set_wino before packing to switch)
+    direct = torch.empty(rows, k_pad, dtype=dtype, device=w.device)
+    fn = lib().pu_pack_weight_bf16 if dtype == BF16 else lib().pu_pack_weight
+    with _Rec("pack_weight", nbytes=4.0 * w.numel() + direct.element_size() * direct.numel()):
+        check(fn(w.data_ptr(), direct.data_ptr(), mode, d0, d1, kh, kw, k_pad, cgroup, _stream()), "pu_pack_weight")
+    planes = wino = None
+    if dtype == torch.float32 and _FP32_MATH == "split6" and k_pad % 16 == 0:
+        planes = split_weight6(direct)
+        # U only while Winograd dispatch is on, so a PU_WINO=0 run neither holds nor refreshes it
+        # (set_wino before packing to switch)
         if _WINO and wino_wanted(w, mode):
             n, c = (d0, d1) if mode == 0 else (d1, d0)
-            out._wino = torch.empty(lib().pu_wino_bytes(n, c) // 2, dtype=BF16, device=w.device)
-            pack_wino([(w, out._wino, mode == 1)])
-            # the direct operand of a layer that only ever runs on Winograd is not refreshed after
-            # the optimizer step (trunk._Packs.refresh); igemm repacks it on the first call that
-            # takes the direct kernel (_ensure_direct)
-            out._src, out._direct_ok, out._wino_only = w, True, True
-        elif hasattr(out, "_wino"):
-            # a U packed from the old weights must not outlive them: repacked in place with
-            # Winograd off, then Winograd back on, igemm would otherwise run on the stale U
-            del out._wino
-            # no Winograd path any more: the direct operand is the one igemm uses, refreshed
-            # every step like any other (trunk._Packs.refresh)
-            out._wino_only, out._direct_ok = False, True
-    out._pack_spec = (mode, k_pad, cgroup)    # pack_weights() refreshes it in place
-    return out
+            wino = torch.empty(lib().pu_wino_bytes(n, c) // 2, dtype=BF16, device=w.device)
+            pack_wino([(w, wino, mode == 1)])
+    return packs.PackedWeight(w, mode, k_pad, cgroup, direct, planes, wino)
 
 
 def pack_weights(jobs, wino=True):
-    """Refresh many packed operands in one launch (pu_pack_weights).  jobs: (w, packed, planes) with
-    ``packed`` an output of pack_weight (fp32 or bf16; its mode / k_pad / cgroup are read from the
-    attributes pack_weight stored on it) and ``planes`` its split6 planes or None.  wino: also
-    refresh the Winograd operands the packed operands carry (one more launch)."""
+    """Refresh many packed operands (PackedWeight) from their parameters in one launch
+    (pu_pack_weights: direct and planes).  wino: also refresh the Winograd operands they carry (one
+    more launch)."""
     if not jobs:
         return
     arr = (PackJob * len(jobs))()
     nbytes = 0.0
-    for i, (w, packed, planes) in enumerate(jobs):
+    for i, p in enumerate(jobs):
+        w, packed, planes = p.src, p.direct, p.planes
         _req(w, "w")
-        mode, k_pad, cg = packed._pack_spec
         d0, d1, kh, kw = w.shape
-        bf = packed.dtype == BF16
+        bf = p.dtype == BF16
         arr[i] = PackJob(w.data_ptr(), None if bf else packed.data_ptr(), packed.data_ptr() if bf else None,
-                         None if planes is None else planes.data_ptr(), mode, d0, d1, kh, kw, k_pad, cg)
+                         None if planes is None else planes.data_ptr(), p.mode, d0, d1, kh, kw, p.k_pad, p.cgroup)
         nbytes += 4.0 * w.numel() + packed.element_size() * packed.numel() + (0 if planes is None else 2.0 * planes.numel())
     with _Rec("pack_weight", nbytes=nbytes):
         check(lib().pu_pack_weights(arr, len(jobs), _stream()), "pu_pack_weights")
-    for _, packed, _ in jobs:
-        if hasattr(packed, "_direct_ok"):
-            packed._direct_ok = True
+    for p in jobs:
+        p.direct_repacked()
     if wino:
-        pack_wino([(w, packed._wino, packed._pack_spec[0] == 1) for w, packed, _ in jobs
-                   if getattr(packed, "_wino", None) is not None])
-
-
-_WINO_TAKES = {}    # call signature -> does pu_conv_igemm take the Winograd kernel for it
-
-
-def _ensure_direct(a, weight, key):
-    """A Winograd-carrying operand on a call: if the library takes the direct kernel for this call
-    (pu_conv_igemm_tile's answer, cached per signature), refresh the direct operand if the last
-    repack skipped it, and keep refreshing it from now on."""
-    takes = _WINO_TAKES.get(key)
-    if takes is None:
-        bm, bn, mode, ks = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        check(lib().pu_conv_igemm_tile(ctypes.byref(a), ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(mode),
-                                       ctypes.byref(ks)), "pu_conv_igemm_tile")
-        takes = _WINO_TAKES[key] = mode.value == 6
-    if not takes:
-        weight._wino_only = False
-        if not weight._direct_ok:
-            _refresh_direct(weight)
-
-
-def _refresh_direct(weight):
-    weight._wino_only = False
-    pack_weights([(weight._src, weight, getattr(weight, "_split6", None))], wino=False)
+        pack_wino([(p.src, p.wino, p.mode == 1) for p in jobs if p.wino is not None])
 
 
 def split_weight6(packed):
-    """packed fp32 [n][k_pad] -> bf16 planes [k_pad/16][6][n][8] (hi/mid/lo, exact split)."""
+    """packed fp32 [n][k_pad] (or the PackedWeight holding it as direct) -> bf16 planes
+    [k_pad/16][6][n][8] (hi/mid/lo, exact split)."""
+    if isinstance(packed, packs.PackedWeight):
+        packed = packed.direct
     _req(packed, "packed")
     n, k_pad = packed.shape
     out = torch.empty(k_pad // 16, 6, n, 8, dtype=BF16, device=packed.device)

@@ -24,6 +24,7 @@ import torch
 
 from . import kernels as K
 from ._lib import PU_PACK_CONV_FWD, PU_PACK_CONV_DGRAD, PU_PACK_CONVT_FWD, PU_PACK_CONVT_DGRAD
+from .packs import Packs as _Packs
 
 
 # Weight-gradient side stream: the backward enqueues every weight gradient (and its split
@@ -37,8 +38,6 @@ _SIDE = {"1": True, "0": False}.get(os.environ.get("PU_WSTREAM", ""), "bf16")
 
 # PU_STEM_BF16=0: the bf16 trunk's stem writes fp32 and converts (A/B runs)
 _STEM_BF16 = os.environ.get("PU_STEM_BF16", "1") != "0"
-# PU_LAZY_DIRECT=0: refresh every packed direct operand after each optimizer step (A/B runs)
-_LAZY = os.environ.get("PU_LAZY_DIRECT", "1") != "0"
 
 
 class _OnStream:
@@ -63,45 +62,6 @@ def set_side_stream(on):
     True / False, or "bf16" (the default: bf16 trunks only)."""
     global _SIDE
     _SIDE = on if on == "bf16" else bool(on)
-
-
-class _Packs:
-    """Packed GEMM operands of the OIHW parameters, rebuilt only when a parameter changes.
-
-    The cache keys on the parameter's storage and checks its version counter (the optimizer and
-    the DP broadcast bump it).  ``refresh()`` - called once at the start of every trunk forward -
-    re-packs every stale entry in place with ONE multi-tensor launch (pu_pack_weights: pack + exact
-    bf16 split fused) instead of two launches per operand at first use."""
-
-    def __init__(self):
-        self.cache = {}
-
-    def get(self, w, mode, k_pad, cgroup=0, dtype=torch.float32):
-        # keyed by storage (detached views share the parameter's version counter)
-        key = (w.data_ptr(), tuple(w.shape), mode, cgroup, dtype)
-        ver = w._version
-        hit = self.cache.get(key)
-        if hit is not None and hit[0] == ver and hit[1]._pack_spec[1] == k_pad:
-            return hit[1]
-        packed = K.pack_weight(w.detach(), mode, k_pad, cgroup=cgroup, dtype=dtype)
-        self.cache[key] = (ver, packed, w)
-        return packed
-
-    def refresh(self):
-        stale = [(key, w, packed) for key, (ver, packed, w) in self.cache.items()
-                 if w._version != ver and w.data_ptr() == key[0]]
-        if stale:
-            # operands only ever used by the Winograd kernel get their U refreshed, not the
-            # direct operand (K._ensure_direct repacks it if a call ever needs it)
-            direct = [(w.detach(), packed, getattr(packed, "_split6", None)) for _, w, packed in stale
-                      if not (_LAZY and getattr(packed, "_wino_only", False))]
-            K.pack_weights(direct, wino=False)
-            K.pack_wino([(w.detach(), packed._wino, packed._pack_spec[0] == 1) for _, w, packed in stale
-                         if getattr(packed, "_wino", None) is not None])
-            for key, w, packed in stale:
-                if _LAZY and getattr(packed, "_wino_only", False):
-                    packed._direct_ok = False
-                self.cache[key] = (w._version, packed, w)
 
 
 def _grad_sinks(trunk, outc):

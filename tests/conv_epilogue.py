@@ -471,8 +471,10 @@ def device_inputs(name):
     _, _, k_pad, mode, _, _ = geometry(c)
     d = dict(src0=_dev(v["x0"], dt), src1=_dev(v["x1"], dt) if c.c1 else None)
     w = v["w"].cuda()
-    d["weight"] = K.pack_weight(w, mode, k_pad, cgroup=c.cg, dtype=dt)
-    d["weight6"] = K.split_weight6(d["weight"]) if c.w6 else None
+    packed = K.pack_weight(w, mode, k_pad, cgroup=c.cg, dtype=dt)
+    assert not c.w6 or packed.planes is not None
+    d["weight"] = packed.direct
+    d["weight6"] = packed.planes if c.w6 else None
     d["wino"] = None
     if c.wino:
         d["wino"] = torch.empty(K.lib().pu_wino_bytes(c.n, c.c0 + c.c1) // 2, dtype=BF, device="cuda")

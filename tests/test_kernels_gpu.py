@@ -491,13 +491,15 @@ def test_pack_weights_multi_equals_single_packs(dt):
         k_pad = (kmin + 31) // 32 * 32 if dt == torch.bfloat16 else K.round16(kmin)
         ref = K.pack_weight(w, mode, k_pad, cgroup=cg, dtype=dt)
         out = K.pack_weight(torch.zeros_like(w), mode, k_pad, cgroup=cg, dtype=dt)   # same buffers, zero content
-        jobs.append((w, out, getattr(out, "_split6", None)))
+        out.src = w
+        jobs.append(out)
         refs.append(ref)
     K.pack_weights(jobs)
-    for (w, out, planes), ref in zip(jobs, refs):
-        assert torch.equal(out, ref)
-        if planes is not None:
-            assert torch.equal(planes, ref._split6)
+    for out, ref in zip(jobs, refs):
+        assert torch.equal(out.direct, ref.direct)
+        assert (out.planes is None) == (ref.planes is None)
+        if out.planes is not None:
+            assert torch.equal(out.planes, ref.planes)
 
 
 def test_pack_refresh_after_optimizer_is_one_launch():

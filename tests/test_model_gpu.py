@@ -430,7 +430,7 @@ def test_graph_step_bitwise_equals_eager(precision):
 
 def test_lazy_direct_operands_after_optimizer_steps():
     """After an optimizer step the trunk refreshes only the Winograd operand of a layer that has
-    only ever run on the Winograd kernel (trunk._Packs.refresh); a later call that takes the direct
+    only ever run on the Winograd kernel (punet.packs: Packs.refresh); a later call that takes the direct
     kernel (here: Winograd switched off) must repack the direct operand first.  Compared bit for
     bit with fresh models holding the same weights (they pack everything at first use)."""
     from punet import kernels as K

@@ -84,7 +84,7 @@ def test_wino_fwd_dgrad_vs_fp64(B, H, W, c0, c1, cout):
         xk = nhwc(x).to(DEV)
         x0, x1 = (xk[..., :c0].contiguous(), xk[..., c0:].contiguous()) if c1 else (xk, None)
         wk = w.to(DEV)
-        assert (getattr(pk.get(wk, 0, K.round16(9 * C), K.cgroup_for(c0, c1)), "_wino", None) is not None) \
+        assert (pk.get(wk, 0, K.round16(9 * C), K.cgroup_for(c0, c1)).wino is not None) \
             == K.wino_wanted(wk, 0)
         y = T.conv3x3(x0, wk, b.to(DEV), pk, x1=x1, relu=True)
         check("wino fwd %dx%dx%d %d+%d->%d" % (B, H, W, c0, c1, cout), nchw(y), ref[torch.float32][0],
@@ -94,7 +94,7 @@ def test_wino_fwd_dgrad_vs_fp64(B, H, W, c0, c1, cout):
         dzk = nhwc(dz).to(DEV)
         d0, d1 = T.conv3x3_dgrad(dzk, wk, pk, split=c0 if c1 else None, mask0=x0, mask1=x1)
         dx = torch.cat([d0, d1], 3) if c1 else d0
-        assert (getattr(pk.get(wk, 1, K.round16(9 * cout), K.cgroup_for(cout)), "_wino", None) is not None) \
+        assert (pk.get(wk, 1, K.round16(9 * cout), K.cgroup_for(cout)).wino is not None) \
             == K.wino_wanted(wk, 1)
         check("wino dgrad", nchw(dx), ref[torch.float32][1], ref[torch.float64][1])
     finally:
@@ -108,11 +108,11 @@ def _wino_plan(B, H, W, C, N, x, packed, k_pad, dst, bias=None, resid=None, relu
     from punet import _lib
     flags = (_lib.PU_EPI_RELU if relu else 0) | (_lib.PU_EPI_ACCUM if accum else 0) | \
         (_lib.PU_EPI_RESID if resid is not None else 0)
-    a = _lib.ConvArgs(B, H, W, H, W, 3, 3, 1, 1, x.data_ptr(), C, None, 0, packed.data_ptr(), k_pad,
+    a = _lib.ConvArgs(B, H, W, H, W, 3, 3, 1, 1, x.data_ptr(), C, None, 0, packed.direct.data_ptr(), k_pad,
                       K.cgroup_for(C), N, None if bias is None else bias.data_ptr(), dst.data_ptr(), N, None,
                       None, None, flags, None, 0, None if resid is None else resid.data_ptr())
-    a.weight6 = packed._split6.data_ptr()
-    a.wino = packed._wino.data_ptr()
+    a.weight6 = packed.planes.data_ptr()
+    a.wino = packed.wino.data_ptr()
     L = K.lib()
     nbytes = L.pu_conv_igemm_workspace_bytes(ctypes.byref(a))
     if nbytes:      # planning only reads the pointer's presence and the size
@@ -146,7 +146,7 @@ def _resid_and_accumulate(B, H, W, C, N, item_n, split):
             pk = T._Packs()
             k_pad = K.round16(9 * C)
             packed = pk.get(w, 0, k_pad, K.cgroup_for(C))
-            assert (getattr(packed, "_wino", None) is not None) == on
+            assert (packed.wino is not None) == on
             o1 = torch.empty(B, H, W, N, device=DEV)
             o2 = acc0.clone()
             if on:

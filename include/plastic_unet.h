@@ -25,6 +25,8 @@
  *                                                      (autograd of unet_p.py:69-88, hebb kept live)
  *   pu_bce_fwd/bwd     nn.BCELoss (mean, log >= -100)  src/train.py:70,101-105
  *   pu_adam_multi      torch.optim.Adam.step           src/train.py:66,111
+ *   pu_grad_norm       torch.nn.utils.clip_grad_norm_ (no reference call site: an extension for
+ *   pu_adam_multi_clipped  episode training) - the norm and coefficient, and Adam on the scaled g
  *   pu_bn_fwd/bwd      nn.BatchNorm2d (+ReLU)          src/unet/unet_p.py:186-193 (batch_norm=True)
  *   pu_upsample_bilinear2x_fwd/bwd  nn.Upsample(2, bilinear, align_corners) unet_p.py:235-236
  *   pu_pack_weight     (layout only) OIHW parameters -> the packed GEMM operands
@@ -487,6 +489,27 @@ typedef struct {
 
 int pu_adam_multi(const pu_adam_tensor* tensors, int n_tensors, double beta1, double beta2, double eps,
                   double weight_decay, double step_size, double bc2_sqrt, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, norm_type 2), on the device:
+ *   pu_grad_norm           out2[0] = (float)sqrt(sum of g^2 over every tensor of the list), summed in
+ *                          fp64 in one fixed order (no atomics: the same bits on every call, at every
+ *                          pointer alignment and on every rank that holds the same values);
+ *                          out2[1] = min(1, (float)max_norm / (out2[0] + 1e-6f)), NaN for a NaN norm
+ *   pu_adam_multi_clipped  pu_adam_multi on g * grad_scale[0] (one fp32 rounding, then the update of
+ *                          pu_adam_multi); grad_scale is a device pointer, usually out2 + 1.  The
+ *                          gradients are read, never written.
+ * pu_grad_norm and its workspace query read only `grad` and `numel` of an entry; entries with
+ * numel == 0 are skipped, an all-empty list gives norm 0 and coefficient 1.  max_norm > 0; +inf measures without
+ * clipping.  The workspace holds one double per 4096-element chunk, 8-byte aligned:
+ * 8 * max(1, sum ceil(numel / 4096)) bytes.
+ * ------------------------------------------------------------------------------------------- */
+size_t pu_grad_norm_workspace_bytes(const pu_adam_tensor* tensors, int n_tensors);
+int pu_grad_norm(const pu_adam_tensor* tensors, int n_tensors, double max_norm, float* out2, void* workspace,
+                 size_t workspace_bytes, void* stream);
+int pu_adam_multi_clipped(const pu_adam_tensor* tensors, int n_tensors, double beta1, double beta2, double eps,
+                          double weight_decay, double step_size, double bc2_sqrt, const float* grad_scale,
+                          void* stream);
 
 #ifdef __cplusplus
 }

@@ -145,6 +145,10 @@ SIGNATURES = [
     ("pu_pack_weights", c_int, [ctypes.POINTER(PackJob), c_int, P]),
     ("pu_adam_multi", c_int, [ctypes.POINTER(AdamTensor), c_int, c_double, c_double, c_double, c_double, c_double,
                               c_double, P]),
+    ("pu_grad_norm_workspace_bytes", c_size, [ctypes.POINTER(AdamTensor), c_int]),
+    ("pu_grad_norm", c_int, [ctypes.POINTER(AdamTensor), c_int, c_double, P, P, c_size, P]),
+    ("pu_adam_multi_clipped", c_int, [ctypes.POINTER(AdamTensor), c_int, c_double, c_double, c_double, c_double,
+                                      c_double, c_double, P, P]),
 ]
 
 _lib = None

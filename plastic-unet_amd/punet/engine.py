@@ -25,12 +25,16 @@ from .optim import FusedAdam
 
 class Trainer:
     def __init__(self, net, lr=3e-4, steplr=1e5, gamma=0.666, betas=(0.9, 0.999), eps=1e-8,
-                 flat_grads=True, bucket_mb=16, overlap=True, force_reduce=False, graph=False):
-        """force_reduce: run the overlapped all-reduce path even in a world of one rank (tests the
+                 flat_grads=True, bucket_mb=16, overlap=True, force_reduce=False, graph=False,
+                 max_grad_norm=None):
+        """max_grad_norm: clip the gradients by their global 2-norm inside the Adam step (FusedAdam's
+        max_grad_norm: .grad stays unscaled); every kind of step then leaves its norm, before
+        clipping, in last_grad_norm.  Under data parallelism the norm is taken after the all-reduce.
+        force_reduce: run the overlapped all-reduce path even in a world of one rank (tests the
         RCCL async path on a one-GPU box; an AVG over one rank is the identity)"""
         self.net = net
         self.params = list(net.parameters())
-        self.opt = FusedAdam(net.parameters(), lr=lr, betas=betas, eps=eps)
+        self.opt = FusedAdam(net.parameters(), lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm)
         self.sched = torch.optim.lr_scheduler.StepLR(self.opt, gamma=gamma, step_size=int(steplr))
         self.bucket_mb = bucket_mb
         self.gradbuf = None
@@ -64,6 +68,12 @@ class Trainer:
         # bucket (on a CPU / gloo group: the host wall time of finish()).
         self.measure_allreduce = False
         self.allreduce_log = []
+
+    @property
+    def last_grad_norm(self):
+        """Global gradient norm of the last step as a 0-d device tensor (no host synchronisation),
+        eta's gradient included after step_episode; None when clipping is off or before a step."""
+        return self.opt.grad_norm
 
     def allreduce_info(self):
         """Static bucket layout of the overlapped reducer (None when it is not active)."""

@@ -17,7 +17,7 @@ from ._lib import (ConvArgs, WgradArgs, PlasticArgs, PlasticHeadArgs, PlasticBwd
 
 __all__ = ["KernelProfiler", "igemm", "wgrad", "pack_weight", "nchw_to_nhwc", "maxpool2_fwd", "maxpool2_bwd",
            "outconv_fwd", "outconv_bwd", "plastic_fwd", "trace_update", "plastic_bwd", "plastic_bwd_trace", "bce_fwd",
-           "bce_bwd", "adam_multi", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
+           "bce_bwd", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
 
 
 def lib():
@@ -703,14 +703,43 @@ def bce_bwd(y, t, grad_loss):
     return dy
 
 
-def adam_multi(params, grads, exp_avgs, exp_avg_sqs, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt):
+def grad_norm(grads, max_norm):
+    """Global 2-norm of the gradient tensors and its clipping coefficient (pu_grad_norm) ->
+    float32 [2] on the device: [norm, min(1, max_norm / (norm + 1e-6))].  The sum runs in fp64 in a
+    fixed order: the same bits for the same values wherever the tensors lie.  float('inf') as
+    max_norm measures without clipping."""
+    n = len(grads)
+    if n == 0:
+        raise ValueError("grad_norm: no gradients")
+    arr = (AdamTensor * n)()
+    for i, g in enumerate(grads):
+        _req(g, "grads[%d]" % i)
+        arr[i] = AdamTensor(None, g.data_ptr(), None, None, g.numel())
+    L = lib()
+    nbytes = L.pu_grad_norm_workspace_bytes(arr, n)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=grads[0].device)
+    out = torch.empty(2, dtype=torch.float32, device=grads[0].device)
+    with _Rec("grad_norm", nbytes=4.0 * sum(g.numel() for g in grads) + float(nbytes)):
+        check(L.pu_grad_norm(arr, n, max_norm, out.data_ptr(), ws.data_ptr(), nbytes, _stream()), "pu_grad_norm")
+    return out
+
+
+def adam_multi(params, grads, exp_avgs, exp_avg_sqs, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt,
+               grad_scale=None):
+    """grad_scale: a float32 device tensor whose first element multiplies every gradient as it is
+    read (pu_adam_multi_clipped; the gradients themselves stay as they are); None: pu_adam_multi."""
     n = len(params)
     arr = (AdamTensor * max(n, 1))()
     for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
         arr[i] = AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
     with _Rec("adam", nbytes=28.0 * sum(p.numel() for p in params)):
-        check(lib().pu_adam_multi(arr, n, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, _stream()),
-              "pu_adam_multi")
+        if grad_scale is None:
+            check(lib().pu_adam_multi(arr, n, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, _stream()),
+                  "pu_adam_multi")
+        else:
+            _req(grad_scale, "grad_scale")
+            check(lib().pu_adam_multi_clipped(arr, n, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt,
+                                              grad_scale.data_ptr(), _stream()), "pu_adam_multi_clipped")
 
 
 # --------------------------------------------------------------------- BatchNorm2d / bilinear 2x

@@ -11,6 +11,8 @@ save checkpoints (:153-203).  Differences, all opt-in:
   --synthetic N / --dataset FILE.npz   input data besides --data DIR (the TGS PNG layout, utils/data_set.py)
   --bptt K         episodes of K consecutive batches with the plastic trace kept live: one backward
                    through the K trace updates (truncated BPTT), one Adam step per episode; eta learns
+  --clip-grad X    clip the gradients of every step to the global 2-norm X, on the device inside the
+                   Adam step; the per-step norms are logged as train/grad_norms (0: off)
   --resident       keep the whole training set in HBM; default: batches stream host -> HBM through
                    pinned, double-buffered asynchronous copies (punet/loader.py) under the previous step
 Data-parallel training: launch with torch.distributed.run; each rank trains its contiguous shard
@@ -65,9 +67,14 @@ def train(net, X_train, X_val, y_train, y_val, params):
         raise ValueError("bptt > 0 needs a net built with trace_grad=True")
     device = params["device"]
     all_losses, val_train_losses, val_test_losses, val_accuracies = [], [], [], []
+    clip_grad = float(params.get("clip_grad", 0) or 0)
+    if clip_grad < 0:
+        raise ValueError("clip_grad must be >= 0 (0: off), got %r" % clip_grad)
+    all_grad_norms = []
     samples_count = len(X_train)
     loss_between_saves, last_save_epoch = 0.0, 0
-    trainer = Trainer(net, lr=params["lr"], steplr=params["steplr"], gamma=params["gamma"])
+    trainer = Trainer(net, lr=params["lr"], steplr=params["steplr"], gamma=params["gamma"],
+                      max_grad_norm=clip_grad if clip_grad > 0 else None)
     ranges = list(_batches(samples_count, bs, world, rank))
     if params.get("prefetch", True):
         # stream batches host -> HBM (pinned, double-buffered, overlapping the previous step)
@@ -88,13 +95,19 @@ def train(net, X_train, X_val, y_train, y_val, params):
         # trace reset per epoch (train.py:88): per-slot traces, or one trace threaded through
         hebb = net.initialZeroHebb() if seq else net.initialZeroHebb(bs)
         losses_dev = []
+        norms_dev = []
         episode = []
+
+        def note_norm():
+            if trainer.last_grad_norm is not None:      # a fresh device scalar per step: no sync here
+                norms_dev.append(trainer.last_grad_norm)
 
         def run_episode(hebb):
             # K consecutive full batches, the trace live across them (truncated BPTT); the copies
             # keep the batches alive while the prefetcher refills its slots
             losses, h = trainer.step_episode([e[0] for e in episode], [e[1] for e in episode], hebb)
             losses_dev.extend(losses.unbind(0))
+            note_norm()
             episode.clear()
             return h
 
@@ -111,6 +124,7 @@ def train(net, X_train, X_val, y_train, y_val, params):
                     hebb = run_episode(hebb)
                 losses, _ = trainer.step_episode([x], [t], hebb[: hi - lo])
                 losses_dev.extend(losses.unbind(0))
+                note_norm()
                 continue
             if seq:
                 loss, hebb = trainer.step(x, t, hebb)
@@ -120,11 +134,14 @@ def train(net, X_train, X_val, y_train, y_val, params):
                 if hi - lo == bs:
                     hebb = h
             losses_dev.append(loss)
+            note_norm()
         if episode:             # the epoch's tail episode may be shorter
             hebb = run_episode(hebb)
         # one host sync per epoch instead of loss.item() per sample (train.py:106)
         epoch_losses = torch.stack(losses_dev).cpu().tolist() if losses_dev else []
         all_losses.extend(epoch_losses)
+        if norms_dev:
+            all_grad_norms.extend(torch.stack(norms_dev).cpu().tolist())
         epoch_loss = np.mean(all_losses[-max(1, len(epoch_losses))]) if all_losses else float("nan")  # S16
         loss_between_saves += epoch_loss
         epoch_time = time.time() - epoch_start_time
@@ -148,7 +165,8 @@ def train(net, X_train, X_val, y_train, y_val, params):
             prefix = params["out_dir"] + "/train"
             if (epoch + 1) % params["rollout"] == 0 and not terminate:
                 prefix = prefix + "_" + str(epoch + 1)
-            np.savez_compressed(prefix + "_data.npz", **{
+            extra = {"train/grad_norms": np.asarray(all_grad_norms)} if clip_grad > 0 else {}
+            np.savez_compressed(prefix + "_data.npz", **extra, **{
                 "net/w": net.w.data.cpu().numpy(), "net/alpha": net.alpha.data.cpu().numpy(),
                 "net/eta": net.eta.data.cpu().numpy(), "train/all_losses": np.asarray(all_losses),
                 "validation/train_losses": np.asarray(val_train_losses),
@@ -169,7 +187,7 @@ def start_train(x_train, x_valid, y_train, y_valid, out_dir, model, img_width, i
                 max_train_time=-1, load=False, gpu=True, epochs=5, lr=3e-5, val_ratio=0.05, val_every=50,
                 save_every=100, gamma=0.666, steplr=1e6, rollout=50000, prule="hebb", debug=False,
                 model_type="unetpres", depth=5, base_ch=8, neurons=16, batch_size=1, hebb_mode="slots",
-                batch_norm=False, bilinear_upsample=False, prefetch=True, bptt=0):
+                batch_norm=False, bilinear_upsample=False, prefetch=True, bptt=0, clip_grad=0.0):
     world, rank, local = dp.init_from_env()
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
@@ -178,7 +196,7 @@ def start_train(x_train, x_valid, y_train, y_valid, out_dir, model, img_width, i
               "val_ratio": val_ratio, "val_every": val_every, "save_every": save_every, "rollout": rollout,
               "gamma": gamma, "steplr": steplr, "prule": prule, "im_width": img_width, "im_height": img_height,
               "im_chan": img_chan, "debug": debug, "batch_size": batch_size, "prefetch": prefetch,
-              "bptt": bptt}
+              "bptt": bptt, "clip_grad": clip_grad}
     if model_type == "unetp":
         net = UNetp(n_channels=img_chan, n_classes=1, nbf=img_width, batch_norm=batch_norm,
                     bilinear_upsample=bilinear_upsample, device=device, rule=prule, depth=depth, base_ch=base_ch,
@@ -235,6 +253,9 @@ def parse_args(argv=None):
     parser.add_option('--bptt', dest='bptt', type='int', default=0,
                       help='K > 0: train on episodes of K consecutive batches with the plastic trace kept live '
                            '(truncated backpropagation through time; eta is learned); 0: the reference loop')
+    parser.add_option('--clip-grad', dest='clip_grad', type='float', default=0.0,
+                      help='X > 0: clip the gradients of every step to the global 2-norm X (device-side, fused '
+                           'into the Adam step) and log the per-step norms; 0: off')
     parser.add_option('--seed', dest='seed', type='int', default=0)
     parser.add_option('--resident', dest='resident', action='store_true', default=False,
                       help='copy the whole training set to HBM once instead of streaming batches')
@@ -273,4 +294,4 @@ if __name__ == '__main__':
                 debug=args.debug, model_type=args.model_type, depth=args.depth, base_ch=args.base_ch,
                 neurons=args.neurons, batch_size=args.batch_size, hebb_mode=args.hebb_mode,
                 batch_norm=args.batch_norm, bilinear_upsample=args.bilinear, prefetch=not args.resident,
-                bptt=args.bptt)
+                bptt=args.bptt, clip_grad=args.clip_grad)

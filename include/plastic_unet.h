@@ -24,6 +24,8 @@
  *   pu_plastic_bwd_trace  the same with dL/dhebb' flowing back: dx, dw, dalpha, dhebb, deta
  *                                                      (autograd of unet_p.py:69-88, hebb kept live)
  *   pu_bce_fwd/bwd     nn.BCELoss (mean, log >= -100)  src/train.py:70,101-105
+ *   pu_seg_metrics     the per-sample BCE, fast_iou_metric and iou_metric_batch counts of validation
+ *                                                      src/eval.py:20-64,66-103
  *   pu_adam_multi      torch.optim.Adam.step           src/train.py:66,111
  *   pu_grad_norm       torch.nn.utils.clip_grad_norm_ (no reference call site: an extension for
  *   pu_adam_multi_clipped  episode training) - the norm and coefficient, and Adam on the scaled g
@@ -468,6 +470,32 @@ int pu_bce_fwd(const float* y, const float* t, long long n, float* loss, void* w
                size_t workspace_bytes, void* stream);
 int pu_bce_bwd(const float* y, const float* t, long long n, const float* grad_loss, float* dy,
                void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Validation metrics of `batch` probability maps y against their targets t, n pixels each (both
+ * [batch][n], contiguous), in one pass.  Per sample b:
+ *   loss[b]    the mean BCE of the sample, bit for bit what pu_bce_fwd gives on y + b*n, t + b*n, n
+ *              (the same grid, element order, fp64 sums and finish; csrc/bce_common.h)
+ *   counts[b]  a row of 2 + 2*n_thr int64:  agree, tcount, pcount[0..n_thr), icount[0..n_thr)
+ *     agree      pixels with (t > 0) == (y > 0.5f): utils.fast_iou_metric on the flattened sample is
+ *                agree / n
+ *     tcount     foreground targets, 0.5 <= t <= 1 (the upper bin of np.histogram(bins=[0, 0.5, 1]))
+ *     pcount[k]  pixels with (double)y > thresholds[k] - the fp64 comparison NumPy makes between an
+ *                fp32 array and a float64 scalar.  The entry rounds thresholds[k] up to the smallest
+ *                fp32 above it and the kernel tests y >= that: the same set of y, NaN and infinities
+ *                included
+ *     icount[k]  those of pcount[k] that are foreground targets too
+ *   utils.iou_score_from_counts(icount[:, k], tcount, pcount[:, k]) is iou_metric_batch(t, y > th_k).
+ * thresholds: n_thr <= 32 HOST doubles, finite and strictly ascending (NULL when n_thr == 0).  They
+ * travel by value in the kernel arguments: no copy, graph-capturable.  The counts are integer sums
+ * (any order gives the same bits); no atomics.  1 <= batch <= 65535, 1 <= n <= 2^40.  The workspace
+ * (8-byte aligned) holds one double and 2 + 2*n_thr uint32 per block:
+ * batch * min(512, ceil(n / 256)) * (8 + 4 * (2 + 2*n_thr)) bytes; the query gives 0 for a shape the
+ * entry rejects.
+ * ------------------------------------------------------------------------------------------- */
+size_t pu_seg_metrics_workspace_bytes(int batch, long long n, int n_thr);
+int pu_seg_metrics(const float* y, const float* t, int batch, long long n, const double* thresholds, int n_thr,
+                   float* loss, long long* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-tensor Adam (torch.optim.Adam, amsgrad=False, maximize=False):

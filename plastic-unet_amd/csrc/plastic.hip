@@ -9,6 +9,7 @@
 //
 // Element-wise formulas keep the reference's operation order with FP contraction off, so the
 // trace update is bit-identical to the ATen CPU ops for the same inputs.
+#include "bce_common.h"   // the BCE element, tree and finish, shared with metrics.hip
 #include "common.h"
 
 #include <math.h>
@@ -967,39 +968,18 @@ __global__ __launch_bounds__(256) void head_dh_kernel(const float* __restrict__ 
 }
 
 // --------------------------------------------------------------------------------------------- BCE
-constexpr int BCE_BLOCKS = 512;
-
 __global__ void bce_partial_kernel(const float* __restrict__ y, const float* __restrict__ t, long long n,
                                    double* __restrict__ partial) {
-#pragma clang fp contract(off)
-    __shared__ double red[256];
     double s = 0.0;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float yy = y[i], tt = t[i];
-        // ATen: (t - 1) * max(log1p(-y), -100) - t * max(log(y), -100)
-        const float l = (tt - 1.f) * fmaxf(log1pf(-yy), -100.f) - tt * fmaxf(logf(yy), -100.f);
-        s += (double)l;
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        s += (double)bce_element(y[i], t[i]);
+    s = bce_block_tree(s);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 __global__ void bce_final_kernel(const double* __restrict__ partial, int np, long long n, float* __restrict__ loss) {
-    __shared__ double red[256];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < np; i += blockDim.x) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)n);
+    const float mean = bce_finish(partial, np, n);
+    if (threadIdx.x == 0) loss[0] = mean;
 }
 
 __global__ void bce_bwd_kernel(const float* __restrict__ y, const float* __restrict__ t, long long n,
@@ -1302,7 +1282,7 @@ extern "C" int pu_bce_fwd(const float* y, const float* t, long long n, float* lo
     PU_REQUIRE(y && t && loss && n > 0, "pu_bce_fwd: bad args");
     if (!workspace || ws_bytes < pu_bce_workspace_bytes(n)) return fail(PU_ERR_WORKSPACE, "pu_bce_fwd: workspace");
     PU_REQUIRE(((uintptr_t)workspace & 7) == 0, "pu_bce_fwd: workspace must be 8-byte aligned");   // fp64 partials
-    int blocks = grid_for(n, 256, BCE_BLOCKS);
+    int blocks = bce_grid(n);
     hipLaunchKernelGGL(bce_partial_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), y, t, n, (double*)workspace);
     hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, as_stream(stream), (const double*)workspace, blocks, n,
                        loss);

@@ -3,7 +3,9 @@
 The reference evaluates one sample at a time with a ZERO trace whose update is discarded (S5), a
 BCE loss and fast_iou_metric on the host.  Here the samples go through the HIP forward in chunks
 of ``batch`` slots (each slot with a zero trace - identical per-sample math), and the per-sample
-loss / metric averages are the reference's.
+loss / metric averages are the reference's.  By default the loss and the pixel counts the metrics
+are made of come from one kernel call per chunk (kernels.seg_metrics) and one small table crosses
+to the host per pass; metrics="host" keeps the numpy path, which gives the same bits.
 """
 from optparse import OptionParser
 
@@ -11,26 +13,63 @@ import numpy as np
 import torch
 
 from punet import bce_loss
-from utils import fast_iou_metric, iou_metric_batch
+from punet import kernels as K
+from punet import metrics as pm
+from utils import fast_iou_metric, iou_metric_batch, iou_score_from_counts
 
 
 def _device_of(net):
     return next(net.parameters()).device
 
 
-def eval_net(net, X_val, y_val, device, criterion=None, debug=False, batch=32):
-    """Returns (accuracy, loss) averaged over samples, as eval.py:66-103."""
+def _check_metrics(metrics):
+    if metrics not in ("device", "host"):
+        raise ValueError("metrics must be 'device' or 'host', not %r" % (metrics,))
+
+
+def _forward_chunk(net, X, y, s, e, device):
+    """Zero-trace forward of samples [s, e): (probabilities [B, n], targets [B, n]) on the device."""
+    xb = torch.from_numpy(np.asarray(X[s:e], dtype=np.float32)).to(device)
+    tb = torch.from_numpy(np.asarray(y[s:e], dtype=np.float32)).to(device)
+    B = xb.shape[0]
+    out, _ = net(xb, net.initialZeroHebb(B))          # zero trace per slot; the update is discarded
+    return out.reshape(B, -1), tb.reshape(B, -1)
+
+
+def eval_net(net, X_val, y_val, device, criterion=None, debug=False, batch=32, metrics="device"):
+    """Returns (accuracy, loss) averaged over samples, as eval.py:66-103.
+
+    metrics="device" (default, with criterion None): one kernels.seg_metrics call per chunk gives the
+    per-sample loss (the bits of bce_loss on the sample) and the count of pixels on which target and
+    thresholded prediction agree - fast_iou_metric on flattened vectors is exactly that count over
+    the pixels -; one table comes back at the end and the host adds in sample order as before, so
+    the two floats are the host path's, bit for bit.  With torch.distributed initialised on more
+    than one rank (every rank calls this with the same data, as train.train does) the chunks are
+    dealt round-robin to the ranks and merged by one all-reduce: every rank returns the same two
+    numbers, the single process's.  metrics="host", or any criterion: the loss per slot and
+    fast_iou_metric in numpy, every rank over the whole set."""
+    _check_metrics(metrics)
     net.eval()
     n = len(X_val)
     total_acc, total_loss = 0.0, 0.0
+    if criterion is None and metrics == "device":
+        world, rank = pm.world_and_rank()
+        table = pm.MetricTable(n, 0, device)
+        with torch.no_grad():
+            for s, e in pm.chunks_for_rank(n, batch, world, rank):
+                yf, tf = _forward_chunk(net, X_val, y_val, s, e, device)
+                table.add(s, *K.seg_metrics(yf, tf))
+        table.finish()
+        pixels = int(np.asarray(y_val[0]).size) if n else 1
+        for sample_loss in table.losses().tolist():
+            total_loss += sample_loss
+        for agree in table.agree().tolist():
+            total_acc += agree / pixels
+        return total_acc / n, total_loss / n
     with torch.no_grad():
         for s in range(0, n, batch):
-            xb = torch.from_numpy(np.asarray(X_val[s:s + batch], dtype=np.float32)).to(device)
-            tb = torch.from_numpy(np.asarray(y_val[s:s + batch], dtype=np.float32)).to(device)
-            B = xb.shape[0]
-            hebb = net.initialZeroHebb(B)          # zero trace per slot; the update is discarded
-            y, _ = net(xb, hebb)
-            yf, tf = y.reshape(B, -1), tb.reshape(B, -1)
+            yf, tf = _forward_chunk(net, X_val, y_val, s, s + batch, device)
+            B = yf.shape[0]
             losses = torch.stack([criterion(yf[b], tf[b]) if criterion is not None else bce_loss(yf[b], tf[b])
                                   for b in range(B)])
             # one device->host copy per chunk; the per-sample sums in the reference's order
@@ -42,25 +81,55 @@ def eval_net(net, X_val, y_val, device, criterion=None, debug=False, batch=32):
     return total_acc / n, total_loss / n
 
 
-def score_model_best_iou(net, X_valid, y_valid, device, debug=False, batch=32):
+def iou_sweep(net, X, y, device, thresholds, batch=32, metrics="device"):
+    """The competition IoU score (iou_metric_batch) of the zero-trace predictions at every threshold:
+    a float32 array, one score per threshold.
+
+    metrics="device" (default): the targets go up per chunk next to the images, kernels.seg_metrics
+    counts per sample and threshold the predicted pixels and those that are foreground targets too,
+    and nothing but the count table comes back; utils.iou_score_from_counts - the tail of
+    iou_metric_batch - turns the counts into the scores.  The thresholds must be strictly ascending
+    (32 per kernel call; a longer list takes more calls).  metrics="host": every prediction comes
+    back and iou_metric_batch runs per threshold in numpy.  The same bits either way.  Always the
+    whole set on the calling process, whatever the process group."""
+    _check_metrics(metrics)
+    net.eval()
+    thresholds = [float(th) for th in thresholds]
+    if metrics == "host":
+        preds = []
+        with torch.no_grad():
+            for s in range(0, len(X), batch):
+                xb = torch.from_numpy(np.asarray(X[s:s + batch], dtype=np.float32)).to(device)
+                out, _ = net(xb, net.initialZeroHebb(xb.shape[0]))
+                preds.append(out.cpu().numpy().reshape(xb.shape[0], 1, 1, out.shape[-2], out.shape[-1]))
+        preds = np.concatenate(preds, 0)
+        return np.array([iou_metric_batch(y, preds > np.float64(th)) for th in thresholds])
+    n = len(X)
+    groups = [thresholds[k:k + 32] for k in range(0, len(thresholds), 32)]
+    tables = [pm.MetricTable(n, len(g), device) for g in groups]
+    with torch.no_grad():
+        for s, e in pm.chunks_for_rank(n, batch):
+            yf, tf = _forward_chunk(net, X, y, s, e, device)
+            for g, table in zip(groups, tables):
+                table.add(s, *K.seg_metrics(yf, tf, g))
+    scores = []
+    for g, table in zip(groups, tables):
+        table.finish(across_ranks=False)
+        scores += [iou_score_from_counts(table.icount(k), table.tcount(), table.pcount(k)) for k in range(len(g))]
+    return np.array(scores)
+
+
+def score_model_best_iou(net, X_valid, y_valid, device, debug=False, batch=32, metrics="device"):
     """Threshold search by the best competition IoU (eval.py:20-64): zero-trace forward of every
     validation sample, 31 thresholds linspace(0.3, 0.7) mapped through the logit as the reference
-    does, iou_metric_batch per threshold; returns (threshold_best, iou_best).
+    does, the score of iou_sweep per threshold; returns (threshold_best, iou_best).
 
     The reference compares its Python LIST of predictions with a float (eval.py:52), which raises
-    TypeError on Python 3; here the predictions are one array [N, 1, 1, H, W] - the
-    comparison the reference intends - so the search completes."""
-    net.eval()
-    preds = []
-    with torch.no_grad():
-        for s in range(0, len(X_valid), batch):
-            xb = torch.from_numpy(np.asarray(X_valid[s:s + batch], dtype=np.float32)).to(device)
-            y, _ = net(xb, net.initialZeroHebb(xb.shape[0]))
-            preds.append(y.cpu().numpy().reshape(xb.shape[0], 1, 1, y.shape[-2], y.shape[-1]))
-    preds_valid = np.concatenate(preds, 0)
+    TypeError on Python 3; here the predictions are compared as one array
+    [N, 1, 1, H, W] - the comparison the reference intends - so the search completes."""
     thresholds_ori = np.linspace(0.3, 0.7, 31)
     thresholds = np.log(thresholds_ori / (1 - thresholds_ori))
-    ious = np.array([iou_metric_batch(y_valid, preds_valid > th) for th in thresholds])
+    ious = iou_sweep(net, X_valid, y_valid, device, thresholds, batch=batch, metrics=metrics)
     if debug:
         print(ious)
     k = int(np.argmax(ious))

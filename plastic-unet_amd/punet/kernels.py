@@ -17,7 +17,7 @@ from ._lib import (ConvArgs, WgradArgs, PlasticArgs, PlasticHeadArgs, PlasticBwd
 
 __all__ = ["KernelProfiler", "igemm", "wgrad", "pack_weight", "nchw_to_nhwc", "maxpool2_fwd", "maxpool2_bwd",
            "outconv_fwd", "outconv_bwd", "plastic_fwd", "trace_update", "plastic_bwd", "plastic_bwd_trace", "bce_fwd",
-           "bce_bwd", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
+           "bce_bwd", "seg_metrics", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
 
 
 def lib():
@@ -701,6 +701,32 @@ def bce_bwd(y, t, grad_loss):
     g = grad_loss.contiguous() if grad_loss is not None else None
     check(lib().pu_bce_bwd(y.data_ptr(), t.data_ptr(), y.numel(), _p(g), dy.data_ptr(), _stream()), "pu_bce_bwd")
     return dy
+
+
+def seg_metrics(y, t, thresholds=()):
+    """Validation metrics of a batch in one pass (pu_seg_metrics): y and t of one size with a leading
+    batch axis B -> (loss [B] float32, counts [B, 2 + 2 T] int64) on the device.  loss[b] has the
+    bits of bce_fwd(y[b], t[b]); a counts row is agree, tcount, pcount[0..T), icount[0..T) - see
+    plastic_unet.h.  thresholds: up to 32 ascending host floats, compared as NumPy compares an fp32
+    array with a float64 scalar."""
+    _req(y, "y"); _req(t, "t")
+    if y.dim() < 1 or y.shape[0] == 0:
+        raise ValueError("seg_metrics: y needs a leading batch axis (got shape %s)" % (tuple(y.shape),))
+    if t.numel() != y.numel():
+        raise ValueError("Target size (%s) must be the same as input size (%s)" % (tuple(t.shape), tuple(y.shape)))
+    B = y.shape[0]
+    n = y.numel() // B
+    T = len(thresholds)
+    th = (ctypes.c_double * max(T, 1))(*[float(v) for v in thresholds])
+    L = lib()
+    nbytes = L.pu_seg_metrics_workspace_bytes(B, n, T)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=y.device)
+    loss = torch.empty(B, dtype=torch.float32, device=y.device)
+    counts = torch.empty((B, 2 + 2 * T), dtype=torch.int64, device=y.device)
+    with _Rec("seg_metrics", nbytes=8.0 * y.numel() + float(nbytes)):
+        check(L.pu_seg_metrics(y.data_ptr(), t.data_ptr(), B, n, th if T else None, T, loss.data_ptr(), counts.data_ptr(),
+                               ws.data_ptr(), nbytes, _stream()), "pu_seg_metrics")
+    return loss, counts
 
 
 def grad_norm(grads, max_norm):

@@ -152,6 +152,7 @@ def train(net, X_train, X_val, y_train, y_val, params):
             print("Epoch finished! Loss: %f, time spent: %d, terminate due to time limits: %s"
                   % (epoch_loss, epoch_time, terminate))
         if (epoch + 1) % params["val_every"] == 0 or terminate:
+            # every rank calls it: the chunks are dealt to the ranks and merged, each evaluated once
             val_acc, val_loss = eval_net(net, X_val, y_val, device)
             val_train_losses.append(epoch_loss)
             val_test_losses.append(val_loss)

@@ -41,8 +41,16 @@ def iou_metric_batch(y_true_in, y_pred_in):
     n = yt.shape[0]
     t = _foreground(yt.reshape(n, -1))
     p = _foreground(yp.reshape(n, -1))
-    inter = np.logical_and(t, p).sum(axis=1).astype(np.float64)
-    union = (t.sum(axis=1) + p.sum(axis=1)).astype(np.float64) - inter
+    return iou_score_from_counts(np.logical_and(t, p).sum(axis=1), t.sum(axis=1), p.sum(axis=1))
+
+
+def iou_score_from_counts(inter, tsum, psum):
+    """iou_metric_batch from the per-sample pixel counts: ``inter`` foreground in both masks, ``tsum``
+    foreground targets, ``psum`` foreground predictions (integer arrays of one length).  The counts
+    are all the score depends on, so they may come from anywhere - iou_metric_batch takes them in
+    numpy, the device path from pu_seg_metrics - and the operations below are the same for both."""
+    inter = np.asarray(inter).astype(np.float64)
+    union = (np.asarray(tsum) + np.asarray(psum)).astype(np.float64) - inter
     inter[inter == 0] = 1e-9
     union[union == 0] = 1e-9
     iou = inter / union

@@ -26,7 +26,9 @@
  *   pu_bce_fwd/bwd     nn.BCELoss (mean, log >= -100)  src/train.py:70,101-105
  *   pu_seg_metrics     the per-sample BCE, fast_iou_metric and iou_metric_batch counts of validation
  *                                                      src/eval.py:20-64,66-103
- *   pu_adam_multi      torch.optim.Adam.step           src/train.py:66,111
+ *   pu_rle_encode      mask > threshold and rle_encode of every test image
+ *                                                      src/infer.py:59-65, src/utils/rle_encode.py:6-17
+ *   pu_adam_multi     torch.optim.Adam.step           src/train.py:66,111
  *   pu_grad_norm       torch.nn.utils.clip_grad_norm_ (no reference call site: an extension for
  *   pu_adam_multi_clipped  episode training) - the norm and coefficient, and Adam on the scaled g
  *   pu_bn_fwd/bwd      nn.BatchNorm2d (+ReLU)          src/unet/unet_p.py:186-193 (batch_norm=True)
@@ -496,6 +498,32 @@ int pu_bce_bwd(const float* y, const float* t, long long n, const float* grad_lo
 size_t pu_seg_metrics_workspace_bytes(int batch, long long n, int n_thr);
 int pu_seg_metrics(const float* y, const float* t, int batch, long long n, const double* thresholds, int n_thr,
                    float* loss, long long* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Submission masks: threshold `batch` probability maps y[batch][h][w] (row-major, contiguous) and
+ * run-length encode each mask as utils.encode does.  For image b:
+ *   mask[i][j] = (double)y[b][i][j] > threshold - NumPy's comparison of an fp32 array with a float64
+ *                scalar; NaN is background, +inf foreground.  For the fp32 comparison NumPy makes with
+ *                a Python float, pass (double)(float)threshold.  As in pu_seg_metrics the entry rounds
+ *                the threshold up to the smallest fp32 above it and the kernel tests y >= that.
+ *   The mask is flattened column-major (p = j*h + i, n = h*w: a run that reaches the bottom of a
+ *   column goes on at the top of the next) and its runs are the pairs (start, length), start 1-based
+ *   and ascending.  An empty mask has no pair, a full one the pair (1, n); no image has more than
+ *   ceil(n / 2).
+ *   offsets[b]  the number of pairs of the images 0 .. b-1; offsets[batch] the total.  Always the true
+ *               counts, whatever cap is.
+ *   runs        the pairs of image b are runs[2*offsets[b] .. 2*offsets[b+1]).  A pair whose index is
+ *               >= cap is not stored, and nothing is written at or past runs + 2*cap (runs may be
+ *               NULL when cap == 0).  cap = batch * ceil(n / 2) never loses a pair.
+ * The threshold (finite) travels by value: no copy, graph-capturable.  No atomics: the order of the
+ * pairs is part of the result.  1 <= batch <= 65535, h, w >= 1, h*w <= 2^30, batch * ceil(n / 2) < 2^31,
+ * cap >= 0.  The workspace (8-byte aligned) holds the transposed bitmap, one 64-bit word per 64 rows
+ * of a column, and one int per image: batch * w * ceil(h / 64) * 8 + batch * 4 bytes; the query gives
+ * 0 for a shape the entry rejects.  Three launches: the bitmap, the counts, the pairs.
+ * ------------------------------------------------------------------------------------------- */
+size_t pu_rle_encode_workspace_bytes(int batch, int h, int w);
+int pu_rle_encode(const float* y, int batch, int h, int w, double threshold, int* offsets, int* runs, long long cap,
+                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-tensor Adam (torch.optim.Adam, amsgrad=False, maximize=False):

@@ -4,7 +4,9 @@
 Forward-only with a zero trace per image (S5); the HIP forward runs in chunks of ``batch`` images
 (each slot with its own zero trace: the per-image math of the reference).  predict() thresholds
 the probabilities, RLE-encodes (column-major, utils/rle_encode.py) and writes the submission CSV
-with the reference's columns (id, rle_mask).  start_inference() builds the reference's model
+with the reference's columns (id, rle_mask).  The threshold and the encoding run on the device
+(predict_rle, kernels.rle_encode: only the runs come to the host); rle="host" is the reference's
+host code on the probability maps.  start_inference() builds the reference's model
 (UNetpRes at the image width), loads the state dict with the weights-only loader, picks the mask
 threshold with eval.score_model_best_iou (whose reference version raises at S12 - see there) and
 predicts.
@@ -16,6 +18,8 @@ from optparse import OptionParser
 import numpy as np
 import torch
 
+from punet import kernels as K
+from punet.rle import RunTable, compare_value
 from utils import encode
 
 
@@ -36,17 +40,50 @@ def predict_masks(net, X, device, batch=32):
     return np.concatenate(out, 0)
 
 
+def _check_rle(rle):
+    if rle not in ("device", "host"):
+        raise ValueError("rle must be 'device' or 'host', not %r" % (rle,))
+
+
+def predict_rle(net, X, device, thr, batch=32, keep=None):
+    """The strings encode(np.round(m > thr)) of the probability masks m of images X [N,C,H,W], with
+    the threshold and the encoding on the device: per chunk only the run table comes back.  Chunk
+    i + 1's forward and encode are enqueued before chunk i's table is read, so the device works while
+    the host prints; the buffers of at most two chunks are alive.  ``keep``: a list that receives each
+    chunk's probability maps on the host (for the PNG masks)."""
+    net.eval()
+    th = compare_value(thr)
+    out, waiting = [], None
+    with torch.no_grad():
+        for s in range(0, len(X), batch):
+            xb = torch.from_numpy(np.asarray(X[s:s + batch], dtype=np.float32)).to(device)
+            y, _ = net(xb, net.initialZeroHebb(xb.shape[0]))
+            table = RunTable(*K.rle_encode(y.contiguous(), th))
+            if waiting is not None:
+                out.extend(waiting.strings())
+            waiting = table
+            if keep is not None:
+                keep.append(y.cpu().numpy())
+    if waiting is not None:
+        out.extend(waiting.strings())
+    return out
+
+
 def _write_mask_png(path, mask):
     from PIL import Image
     tmp = (np.squeeze(mask).astype(np.uint8) * 255)
     Image.fromarray(np.dstack((tmp, tmp, tmp))).save(path)
 
 
-def predict(net, test_df, params, visualize=False, save_masks=False):
+def predict(net, test_df, params, visualize=False, save_masks=False, rle="device"):
     """Threshold + RLE + CSV (infer.py:50-108).  test_df: the reference's test frame (index = image
     ids, column ``images``), or a pair (ids, X_test [N,C,H,W]).  params: out_dir, mask_threshold,
     img_chan/img_height/img_width (to shape the images), subm_file, device (default: the net's).
-    ``visualize`` (matplotlib windows in the reference) is not supported on this host-less path."""
+    ``visualize`` (matplotlib windows in the reference) is not supported on this host-less path.
+    rle: "device" (default) thresholds and encodes on the device, and the probability maps come back
+    only for ``save_masks``; "host" brings every map back and encodes it with utils.encode.  Both give
+    the same rows."""
+    _check_rle(rle)
     if isinstance(test_df, tuple):
         ids, X_test = test_df
         ids = list(ids)
@@ -56,13 +93,21 @@ def predict(net, test_df, params, visualize=False, save_masks=False):
                                                              params["img_width"])
     print("Start prediction with the number of test image samples:", len(ids))
     device = params.get("device") or next(net.parameters()).device
-    masks = predict_masks(net, X_test, device)
     thr = params["mask_threshold"]
+    if rle == "device":
+        kept = [] if save_masks else None
+        codes = predict_rle(net, X_test, device, thr, keep=kept)
+        masks = np.concatenate(kept, 0) if kept else ()
+    else:
+        masks = predict_masks(net, X_test, device)
     if save_masks:
         os.makedirs(os.path.join(params["out_dir"], "masks"), exist_ok=True)
         for fn, m in zip(ids, masks):
             _write_mask_png(os.path.join(params["out_dir"], "masks", "%s.png" % fn), m > thr)
-    rows = [(fn, encode(np.round(m > thr))) for fn, m in zip(ids, masks)]
+    if rle == "device":
+        rows = list(zip(ids, codes))
+    else:
+        rows = [(fn, encode(np.round(m > thr))) for fn, m in zip(ids, masks)]
     path = os.path.join(params["out_dir"], params.get("subm_file", "submission.csv"))
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
@@ -74,12 +119,13 @@ def predict(net, test_df, params, visualize=False, save_masks=False):
 
 def start_inference(model, test_df, X_valid, y_valid, out_dir, img_width, img_height, img_chan,
                     subm_file="submission.csv", gpu=True, visualize=False, save_masks=False, debug=False,
-                    mask_threshold=None, model_type="unetpres"):
+                    mask_threshold=None, model_type="unetpres", rle="device"):
     """infer.py:110-179: the reference builds UNetpRes(n_channels=img_chan, n_classes=1,
     nbf=img_width), loads ``model`` (a state_dict path), scores the best threshold on the
     validation set and predicts.  ``mask_threshold`` skips the threshold search; ``model_type``
     'unetp' loads a UNetp instead.  The product path is the GPU one (``gpu`` is accepted for the
-    signature; there is no CPU fallback)."""
+    signature; there is no CPU fallback).  ``rle``: as in predict."""
+    _check_rle(rle)
     from unet import UNetp, UNetpRes
     import eval as ev
     device = torch.device("cuda")
@@ -96,7 +142,7 @@ def start_inference(model, test_df, X_valid, y_valid, out_dir, img_width, img_he
     os.makedirs(out_dir, exist_ok=True)
     params = {"out_dir": out_dir, "device": device, "img_width": img_width, "img_height": img_height,
               "img_chan": img_chan, "mask_threshold": mask_threshold, "subm_file": subm_file, "debug": debug}
-    return predict(net, test_df, params, visualize=visualize, save_masks=save_masks)
+    return predict(net, test_df, params, visualize=visualize, save_masks=save_masks, rle=rle)
 
 
 def get_args():
@@ -113,6 +159,8 @@ def get_args():
     parser.add_option('--partial', '-p', action='store_true', default=False)
     parser.add_option('--partial-size', '-d', dest='partial_size', default=100, type='int')
     parser.add_option('--model-type', dest='model_type', default='unetpres', help='unetpres | unetp')
+    parser.add_option('--rle', dest='rle', default='device', type='choice', choices=['device', 'host'],
+                      help="where the masks are thresholded and run-length encoded: device | host")
     (options, args) = parser.parse_args()
     return options
 
@@ -133,4 +181,4 @@ if __name__ == "__main__":
     start_inference(model=args.model, test_df=test_df, X_valid=x_valid, y_valid=y_valid, out_dir=args.out_dir,
                     gpu=args.gpu, img_width=w, img_height=h, img_chan=c, visualize=args.visualize,
                     save_masks=args.save, debug=True, mask_threshold=args.mask_threshold,
-                    model_type=args.model_type)
+                    model_type=args.model_type, rle=args.rle)

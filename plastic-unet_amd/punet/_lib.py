@@ -139,6 +139,8 @@ SIGNATURES = [
     ("pu_bce_bwd", c_int, [P, P, c_ll, P, P, P]),
     ("pu_seg_metrics_workspace_bytes", c_size, [c_int, c_ll, c_int]),
     ("pu_seg_metrics", c_int, [P, P, c_int, c_ll, ctypes.POINTER(c_double), c_int, P, P, P, c_size, P]),
+    ("pu_rle_encode_workspace_bytes", c_size, [c_int, c_int, c_int]),
+    ("pu_rle_encode", c_int, [P, c_int, c_int, c_int, c_double, P, P, c_ll, P, c_size, P]),
     ("pu_bn_workspace_bytes", c_size, [c_int, c_ll, c_int]),
     ("pu_bn_fwd", c_int, [P, P, P, P, P, P, P, P, c_int, c_ll, c_int, c_float, c_float, c_int, c_int, P, P, c_size, P]),
     ("pu_bn_bwd", c_int, [P, P, P, P, P, P, P, P, c_int, c_ll, c_int, P, P, P, c_size, P]),

@@ -17,7 +17,7 @@ from ._lib import (ConvArgs, WgradArgs, PlasticArgs, PlasticHeadArgs, PlasticBwd
 
 __all__ = ["KernelProfiler", "igemm", "wgrad", "pack_weight", "nchw_to_nhwc", "maxpool2_fwd", "maxpool2_bwd",
            "outconv_fwd", "outconv_bwd", "plastic_fwd", "trace_update", "plastic_bwd", "plastic_bwd_trace", "bce_fwd",
-           "bce_bwd", "seg_metrics", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
+           "bce_bwd", "seg_metrics", "rle_encode", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
 
 
 def lib():
@@ -727,6 +727,30 @@ def seg_metrics(y, t, thresholds=()):
         check(L.pu_seg_metrics(y.data_ptr(), t.data_ptr(), B, n, th if T else None, T, loss.data_ptr(), counts.data_ptr(),
                                ws.data_ptr(), nbytes, _stream()), "pu_seg_metrics")
     return loss, counts
+
+
+def rle_encode(y, threshold, cap=None):
+    """Threshold and column-major run-length encoding of a batch of maps (pu_rle_encode): y [B, H, W]
+    -> (offsets [B + 1] int32, runs [cap, 2] int32) on the device.  The (start, length) pairs of image
+    b are runs[offsets[b]:offsets[b + 1]], the numbers utils.encode prints for y[b] > threshold.
+    threshold: a host float compared as (double)y > threshold - a compare value, see punet.rle.compare_value.
+    cap: room for that many pairs (default: the worst case, B * ceil(H W / 2)); the offsets are the true
+    ones whatever it is, and pairs from index cap on are not stored."""
+    _req(y, "y")
+    if y.dim() != 3 or y.numel() == 0:
+        raise ValueError("rle_encode: y must be [B, H, W] with no empty axis (got shape %s)" % (tuple(y.shape),))
+    B, H, W = y.shape
+    if cap is None:
+        cap = B * ((H * W + 1) // 2)
+    L = lib()
+    nbytes = L.pu_rle_encode_workspace_bytes(B, H, W)
+    ws = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.int64, device=y.device)
+    offsets = torch.empty(B + 1, dtype=torch.int32, device=y.device)
+    runs = torch.empty((max(cap, 0), 2), dtype=torch.int32, device=y.device)
+    with _Rec("rle_encode", nbytes=4.0 * y.numel() + 2.0 * float(nbytes)):
+        check(L.pu_rle_encode(y.data_ptr(), B, H, W, float(threshold), offsets.data_ptr(), runs.data_ptr() or None, cap,
+                              ws.data_ptr(), nbytes, _stream()), "pu_rle_encode")
+    return offsets, runs
 
 
 def grad_norm(grads, max_norm):

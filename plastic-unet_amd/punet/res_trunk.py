@@ -22,124 +22,21 @@ stride-2 3x3 conv (pad = crop) and its wgrad a stride-2 weight-gradient GEMM; th
 is a column sum.  The concat is [upsampled | skip] (upsampled FIRST, :218) and is read from the
 two buffers directly.  Dropout2d (:209, :248) multiplies channels by a per-sample mask
 (punet.kernels.channel_scale); masks come from torch's generator (``mask_fn`` may inject them).
+
+The layer ops (conv3x3 with its resid / chan_scale epilogues, convT3x3) are punet.layers'; the
+gradient sinks, the BatchNorm and outconv blocks and the autograd node are punet.trunk_base's.
 """
 import torch
 
 from . import kernels as K
-from ._lib import PU_PACK_CONV_FWD, PU_PACK_CONV_DGRAD, PU_PACK_CONVT_DGRAD, PU_PACK_CONVT3_FWD
-from .trunk import _Packs, _grad_sinks
-
-
-# ------------------------------------------------------------------------------ layer helpers
-def conv3x3(x0, w, b, packs, x1=None, relu=True, resid=None):
-    """3x3/p1 conv over [x0 | x1] (NHWC) + bias (+ resid) (then ReLU)."""
-    B, H, W, c0 = x0.shape
-    c1 = 0 if x1 is None else x1.shape[3]
-    cout = w.shape[0]
-    k_pad = K.round16(9 * (c0 + c1))
-    g = K.cgroup_for(c0, c1)
-    out = torch.empty(B, H, W, cout, dtype=torch.float32, device=x0.device)
-    K.igemm(batch=B, in_hw=(H, W), out_hw=(H, W), k=3, stride=1, pad=1, src0=x0, c0=c0, src1=x1, c1=c1,
-            weight=packs.get(w, PU_PACK_CONV_FWD, k_pad, g), k_pad=k_pad, n=cout, bias=b, dst0=out, relu=relu,
-            cgroup=g, resid=resid)
-    return out
-
-
-def conv3x3_dgrad(dz, w, packs, split=None, mask0=None, mask1=None, resid=None, chan_scale=None):
-    """dX = conv(dZ, flipped W^T) (+ resid) (. mask) (* chan_scale[b, c]: the Dropout2d backward);
-    optional channel split -> (d0, d1)."""
-    B, H, W, cout = dz.shape
-    cin = w.shape[1]
-    k_pad = K.round16(9 * cout)
-    g = K.cgroup_for(cout)
-    n0 = cin if split is None else split
-    d0 = torch.empty(B, H, W, n0, dtype=torch.float32, device=dz.device)
-    d1 = None if split is None else torch.empty(B, H, W, cin - n0, dtype=torch.float32, device=dz.device)
-    K.igemm(batch=B, in_hw=(H, W), out_hw=(H, W), k=3, stride=1, pad=1, src0=dz, c0=cout,
-            weight=packs.get(w, PU_PACK_CONV_DGRAD, k_pad, g), k_pad=k_pad, n=cin, dst0=d0, n0=n0, dst1=d1,
-            mask0=mask0, mask1=mask1, cgroup=g, resid=resid, chan_scale=chan_scale)
-    return d0, d1
-
-
-def conv3x3_wgrad(dz, x0, x1=None, out=None):
-    B, H, W, cout = dz.shape
-    c0 = x0.shape[3]
-    c1 = 0 if x1 is None else x1.shape[3]
-    if out is None:
-        dw = torch.empty(cout, c0 + c1, 3, 3, dtype=torch.float32, device=dz.device)
-        db = torch.empty(cout, dtype=torch.float32, device=dz.device)
-    else:
-        dw, db = out
-    K.wgrad(batch=B, in_hw=(H, W), out_hw=(H, W), k=3, stride=1, pad=1, rows=dz, n=cout, src0=x0, c0=c0,
-            src1=x1, c1=c1, bias_mode=1, dweight=dw, dbias=db)
-    return dw, db
-
-
-def _crop(h, out_h):
-    crop = 2 * h + 1 - out_h
-    if crop not in (0, 1):
-        raise RuntimeError("ConvTranspose2d(3, s=2) output %d cannot be padded to the skip size %d "
-                           "(unet_p_res.py:215-217 only ever crops one row)" % (2 * h + 1, out_h))
-    return crop
-
-
-def _fusable(m):
-    """A Dropout2d mask the conv epilogue can apply (float4 rows: width % 4 == 0, 16-byte aligned
-    contiguous rows), else None (a separate pu_channel_scale pass)."""
-    if m is None or m.shape[1] % 4 or not m.is_contiguous() or m.data_ptr() % 16:
-        return None
-    return m
-
-
-def convT3x3(x, w, b, packs, out_hw, chan_scale=None):
-    """ConvTranspose2d(cin, cout, 3, stride=2, padding=0) + crop to out_hw (NHWC); chan_scale
-    [B, >= cout] (row stride = its width): per-(image, channel) factors (the Dropout2d of up())."""
-    B, h, wd, cin = x.shape
-    cout = w.shape[1]
-    H2, W2 = out_hw
-    crop = _crop(h, H2)
-    if _crop(wd, W2) != crop:
-        raise RuntimeError("non-square crop")
-    k_pad = K.round16(4 * cin)
-    out = torch.empty(B, H2, W2, cout, dtype=torch.float32, device=x.device)
-    K.igemm(batch=B, in_hw=(h, wd), out_hw=(h + 1, wd + 1), k=2, stride=1, pad=1, src0=x, c0=cin,
-            weight=packs.get(w, PU_PACK_CONVT3_FWD, k_pad), k_pad=k_pad, n=4 * cout, bias=b, dst0=out,
-            shuffle=True, shuf=(H2, W2, crop), chan_scale=chan_scale)
-    return out
-
-
-def convT3x3_dgrad(du, w, packs, in_hw, mask):
-    """dX[i] = sum_r W[:, :, r] dU_full[2i + r] (dU_full[o] = du[o - crop]), times (mask > 0)."""
-    B, H2, W2, cout = du.shape
-    cin = w.shape[0]
-    h, wd = in_hw
-    crop = _crop(h, H2)
-    k_pad = K.round16(9 * cout)
-    g = K.cgroup_for(cout)
-    dx = torch.empty(B, h, wd, cin, dtype=torch.float32, device=du.device)
-    K.igemm(batch=B, in_hw=(H2, W2), out_hw=(h, wd), k=3, stride=2, pad=crop, src0=du, c0=cout,
-            weight=packs.get(w, PU_PACK_CONVT_DGRAD, k_pad, g), k_pad=k_pad, n=cin, dst0=dx, mask0=mask, cgroup=g)
-    return dx
-
-
-def convT3x3_wgrad(x, du, out=None):
-    """dW[i][o][r][s] = sum_p x[p][i] dU_full[2p + (r, s)][o] ; db[o] = sum over du pixels."""
-    B, h, wd, cin = x.shape
-    _, H2, W2, cout = du.shape
-    crop = _crop(h, H2)
-    if out is None:
-        dw = torch.empty(cin, cout, 3, 3, dtype=torch.float32, device=x.device)
-        db = torch.empty(cout, dtype=torch.float32, device=x.device)
-    else:
-        dw, db = out
-    K.wgrad(batch=B, in_hw=(H2, W2), out_hw=(h, wd), k=3, stride=2, pad=crop, rows=x, n=cin, src0=du, c0=cout,
-            bias_mode=0, dweight=dw)
-    K.column_sum(du.view(-1, cout), out=db)
-    return dw, db
+from .layers import (conv3x3, conv3x3_dgrad, conv3x3_wgrad, convT3x3, convT3x3_dgrad, convT3x3_wgrad,    # noqa: F401
+                     _crop, _fusable)
+from .packs import Packs as _Packs                                                                      # noqa: F401
+from .trunk_base import TrunkBase
 
 
 # --------------------------------------------------------------------------------- the trunk
-class ResTrunk:
+class ResTrunk(TrunkBase):
     """Parameter order and kernel schedule of UNetpRes.  Per stack (conv1..conv4, mid, and the
     middle of uconv4..uconv1): conv0 w,b, block1 A w,b, block1 B w,b, block2 A w,b, block2 B w,b;
     each up stage puts its ConvTranspose2d w,b before its stack; outc w,b last."""
@@ -148,22 +45,20 @@ class ResTrunk:
     UP = ("uconv4", "uconv3", "uconv2", "uconv1")
 
     def __init__(self, model):
-        self.packs = _Packs()
+        super().__init__()
         self.model = model
-        self.params = []
-        self.slots = {}
         for name in self.DOWN + ("mid",):
             mod = getattr(model, name)
             seq = mod.dconv if name != "mid" else mod.mconv
-            self.slots[name] = len(self.params)
+            self.slot[name] = len(self.params)
             self.params += self._stack_params(seq)
         for name in self.UP:
             mod = getattr(model, name)
-            self.slots[name + ".up"] = len(self.params)
+            self.slot[name + ".up"] = len(self.params)
             self.params += [mod.dconv.weight, mod.dconv.bias]
-            self.slots[name] = len(self.params)
+            self.slot[name] = len(self.params)
             self.params += self._stack_params(mod.uconv[1].mconv)
-        self.slots["outc"] = len(self.params)
+        self.slot["outc"] = len(self.params)
         self.params += [model.outc.conv.weight, model.outc.conv.bias]
         # batch_norm=True (unet_p_res.py:171-176): each residual block of the DOWN stacks and mid
         # carries one BatchNorm2d on its ReLU'd input, before conv A (its conv_modules are built
@@ -182,13 +77,9 @@ class ResTrunk:
                     raise NotImplementedError("UNetpRes BatchNorm layout not recognised")
                 self.bn[(name, blk)] = (len(self.params), m)
                 self.params += [m.weight, m.bias]
-        self.training = True
-        self.gradbuf = None
         self.mask_fn = None      # (name, batch, channels, p) -> [B, C] scale; default: bernoulli
         self.mask_gen = None     # torch.Generator for the bernoulli masks (None: torch's default);
                                  # data-parallel Trainers set a per-rank one (punet.dp.rank_generator)
-        self.fused_head = False  # as UNetpTrunk.fused_head
-        self.debug = None
 
     @staticmethod
     def _stack_params(seq):
@@ -204,17 +95,8 @@ class ResTrunk:
     def backward_order(self):
         """Parameters in the order backward() completes their gradients (outc first, conv1 last;
         the BatchNorm affine parameters last - they are small)."""
-        n_core = self.slots["outc"] + 2
+        n_core = self.slot["outc"] + 2
         return list(reversed(self.params[:n_core])) + list(reversed(self.params[n_core:]))
-
-    def _ready(self, i, n=2):
-        """params[i:i+n]'s gradient kernels are enqueued: let an armed BucketReducer know."""
-        gb = self.gradbuf
-        if gb is not None and gb.reducer is not None:
-            gb.ready(*self.params[i:i + n])
-
-    def grad_sinks(self):
-        return _grad_sinks(self, self.slots["outc"])
 
     def _mask(self, name, B, C, p, device):
         if self.mask_fn is not None:
@@ -223,17 +105,6 @@ class ResTrunk:
             1.0 - p, generator=self.mask_gen).div_(1.0 - p)
 
     # ---------------------------------------------------------------------------- forward
-    def _bn(self, P, key, z, relu, resid=None, save=None):
-        j, m = self.bn[key]
-        training = self.training or not m.track_running_stats
-        update = self.training and m.track_running_stats
-        y, mean, rstd = K.bn_fwd(z, P[j], P[j + 1], m.running_mean if (update or not training) else None,
-                                 m.running_var if (update or not training) else None, m.eps, m.momentum, training,
-                                 relu=relu, resid=resid)
-        if update:
-            m.num_batches_tracked.add_(z.shape[0])     # one reference forward per slot
-        return y, (mean, rstd)
-
     def _stack_fwd_bn(self, P, i, name, x0, x1=None):
         """conv0 + ReLU, then per residual block: n = BN(r); a = relu(A(n)); r' = relu(B(a) + r)
         (unet_p_res.py:166-189 with batch_norm=True; the add and ReLU fused in B's epilogue)."""
@@ -242,7 +113,8 @@ class ResTrunk:
         st = {"x0": x0, "x1": x1}
         for blk in (1, 2):
             ia = i + 2 + 4 * (blk - 1)
-            n, sa = self._bn(P, (name, blk), r, relu=False)
+            j, m = self.bn[(name, blk)]
+            n, sa = self._bn_fwd(P, j, m, r, relu=False)
             a = conv3x3(n, P[ia], P[ia + 1], pk)
             r_next = conv3x3(a, P[ia + 2], P[ia + 3], pk, resid=r)
             st[blk] = (r, n, a, sa)
@@ -259,8 +131,8 @@ class ResTrunk:
         y = conv3x3(a2, P[i + 8], P[i + 9], pk, resid=r2)
         return y, (x0, x1, r1, a1, r2, a2, y)
 
-    def forward(self, x, params, save, training):
-        self.training = training       # BatchNorm: per-slot batch statistics vs running statistics
+    def forward(self, x, params, save):
+        training = self.training       # Dropout2d masks; BatchNorm: per-slot vs running statistics
         self.packs.refresh()           # operands of parameters the optimizer moved: one launch
         P = list(params)
         p_drop = self.model.dropout_ratio
@@ -270,9 +142,9 @@ class ResTrunk:
         skips = []
         for k, name in enumerate(self.DOWN):
             if (name, 1) in self.bn:
-                y, st = self._stack_fwd_bn(P, self.slots[name], name, h)
+                y, st = self._stack_fwd_bn(P, self.slot[name], name, h)
             else:
-                y, st = self._stack_fwd(P, self.slots[name], h)
+                y, st = self._stack_fwd(P, self.slot[name], h)
             s[name] = st
             skips.append(y)
             p = p_drop / 2 if k == 0 else p_drop          # pool1 uses dropout_ratio/2 (:39)
@@ -281,13 +153,13 @@ class ResTrunk:
             if drop:
                 s["pool%d.mask" % (k + 1)] = m
         if ("mid", 1) in self.bn:
-            y, st = self._stack_fwd_bn(P, self.slots["mid"], "mid", h)
+            y, st = self._stack_fwd_bn(P, self.slot["mid"], "mid", h)
         else:
-            y, st = self._stack_fwd(P, self.slots["mid"], h)
+            y, st = self._stack_fwd(P, self.slot["mid"], h)
         s["mid"] = st
         for j, name in enumerate(self.UP):
             skip = skips[3 - j]
-            i = self.slots[name + ".up"]
+            i = self.slot[name + ".up"]
             # Dropout2d over cat(u, skip) (unet_p_res.py:69): u's channels scaled by the ConvT
             # epilogue (the mask's row stride spans both parts), the skip's by a scaled copy (the
             # unscaled skip stays for MaxPool2d's backward)
@@ -301,49 +173,35 @@ class ResTrunk:
                     K.channel_scale(u, m[:, :cu].contiguous(), out=u)
                 src1 = K.channel_scale(skip, m[:, cu:].contiguous())
                 s[name + ".mask"] = m
-            y, st = self._stack_fwd(P, self.slots[name], u, src1)
+            y, st = self._stack_fwd(P, self.slot[name], u, src1)
             s[name] = st
         s["skips"] = skips
-        if self.fused_head:
-            return y, (s if save else None)
-        o = self.slots["outc"]
-        logits = K.outconv_fwd(y, P[o].reshape(-1), P[o + 1])
-        return logits, (s if save else None)
+        return self._outc_fwd(y, P), (s if save else None)
 
     # --------------------------------------------------------------------------- backward
+    def _conv_wgrad(self, i, dz, x0, x1, grads, out):
+        """The weight and bias gradient of the 3x3 conv params[i], params[i+1] over [x0 | x1]."""
+        grads[i], grads[i + 1] = conv3x3_wgrad(dz, x0, x1, out=out(i))
+        self._ready(i)
+
     def _stack_bwd(self, P, i, st, g, grads, out, need_dx=True, split=None, mask1=None, chan_scale=None):
         pk = self.packs
         x0, x1, r1, a1, r2, a2, y = st
         dbg = self.debug
-        grads[i + 8], grads[i + 9] = conv3x3_wgrad(g, a2, out=out(i + 8))
-        self._ready(i + 8)
+        self._conv_wgrad(i + 8, g, a2, None, grads, out)
         g_a2, _ = conv3x3_dgrad(g, P[i + 8], pk, mask0=a2)
-        grads[i + 6], grads[i + 7] = conv3x3_wgrad(g_a2, r2, out=out(i + 6))
-        self._ready(i + 6)
+        self._conv_wgrad(i + 6, g_a2, r2, None, grads, out)
         g_o1, _ = conv3x3_dgrad(g_a2, P[i + 6], pk, mask0=r2, resid=g)
-        grads[i + 4], grads[i + 5] = conv3x3_wgrad(g_o1, a1, out=out(i + 4))
-        self._ready(i + 4)
+        self._conv_wgrad(i + 4, g_o1, a1, None, grads, out)
         g_a1, _ = conv3x3_dgrad(g_o1, P[i + 4], pk, mask0=a1)
-        grads[i + 2], grads[i + 3] = conv3x3_wgrad(g_a1, r1, out=out(i + 2))
-        self._ready(i + 2)
+        self._conv_wgrad(i + 2, g_a1, r1, None, grads, out)
         g_z0, _ = conv3x3_dgrad(g_a1, P[i + 2], pk, mask0=r1, resid=g_o1)
-        grads[i], grads[i + 1] = conv3x3_wgrad(g_z0, x0, x1, out=out(i))
-        self._ready(i)
+        self._conv_wgrad(i, g_z0, x0, x1, grads, out)
         if dbg is not None:
             dbg[i] = (g, g_a2, g_o1, g_a1, g_z0)
         if not need_dx:
             return None, None
         return conv3x3_dgrad(g_z0, P[i], pk, split=split, mask1=mask1, chan_scale=chan_scale)
-
-    def _bn_bwd(self, P, key, z, g, stat, out, grads, add=None, mask=None):
-        j, _ = self.bn[key]
-        o = out(j)
-        dgam = torch.empty_like(P[j]) if o is None else o[0]
-        dbet = torch.empty_like(P[j + 1]) if o is None else o[1]
-        dz = K.bn_bwd(z, g, stat[0], stat[1], P[j], dgam, dbet, add=add, mask=mask)
-        grads[j], grads[j + 1] = dgam, dbet
-        self._ready(j)
-        return dz
 
     def _stack_bwd_bn(self, P, i, name, st, g, grads, out, need_dx=True, split=None, mask1=None):
         """g = dL/d(stack output) * (y > 0)."""
@@ -351,16 +209,13 @@ class ResTrunk:
         for blk in (2, 1):
             r, n, a, sa = st[blk]
             ia = i + 2 + 4 * (blk - 1)
-            grads[ia + 2], grads[ia + 3] = conv3x3_wgrad(g, a, out=out(ia + 2))
-            self._ready(ia + 2)
+            self._conv_wgrad(ia + 2, g, a, None, grads, out)
             ga, _ = conv3x3_dgrad(g, P[ia + 2], pk, mask0=a)
-            grads[ia], grads[ia + 1] = conv3x3_wgrad(ga, n, out=out(ia))
-            self._ready(ia)
+            self._conv_wgrad(ia, ga, n, None, grads, out)
             dn, _ = conv3x3_dgrad(ga, P[ia], pk)
             # r feeds the BatchNorm and the residual add: dL/dr = BN^T dn + g, times relu's mask
-            g = self._bn_bwd(P, (name, blk), r, dn, sa, out, grads, add=g, mask=r)
-        grads[i], grads[i + 1] = conv3x3_wgrad(g, st["x0"], st["x1"], out=out(i))
-        self._ready(i)
+            g = self._bn_bwd(P, self.bn[(name, blk)][0], r, dn, sa, out, grads, add=g, mask=r)
+        self._conv_wgrad(i, g, st["x0"], st["x1"], grads, out)
         if not need_dx:
             return None, None
         return conv3x3_dgrad(g, P[i], pk, split=split, mask1=mask1)
@@ -368,20 +223,9 @@ class ResTrunk:
     def backward(self, s, dlogits, params):
         P = list(params)
         grads = [None] * len(P)
-        sink = self.grad_sinks()
-        out = (lambda i: None) if sink is None else (lambda i: (sink[i], sink[i + 1]))  # noqa: E731
+        out = self._sinks()
         skips = s["skips"]
-        o = self.slots["outc"]
-        y_last = s["uconv1"][6]
-        if self.fused_head:
-            g = dlogits                  # the fused head's outconv backward already applied the mask
-        else:
-            oo = out(o)
-            g, dwo, dbo = K.outconv_bwd(y_last, P[o].reshape(-1), dlogits, relu_mask=True,
-                                        out=None if oo is None else (oo[0].view(-1), oo[1]))
-            grads[o] = dwo.view_as(P[o])
-            grads[o + 1] = dbo
-            self._ready(o)
+        g = self._outc_bwd(s["uconv1"][6], dlogits, P, grads, out)
         gskip = [None] * 4
         for j in range(3, -1, -1):                       # uconv1 .. uconv4
             name = self.UP[j]
@@ -390,50 +234,27 @@ class ResTrunk:
             skip = skips[3 - j]
             # the Dropout2d backward of cat(u, skip) in the split data gradient's epilogue
             m = s.get(name + ".mask")
-            g_u, g_sk = self._stack_bwd(P, self.slots[name], st, g, grads, out, split=cu, mask1=skip,
+            g_u, g_sk = self._stack_bwd(P, self.slot[name], st, g, grads, out, split=cu, mask1=skip,
                                         chan_scale=_fusable(m))
             if m is not None and _fusable(m) is None:
                 K.channel_scale(g_u, m[:, :cu].contiguous(), out=g_u)
                 K.channel_scale(g_sk, m[:, cu:].contiguous(), out=g_sk)
             gskip[3 - j] = g_sk
-            i = self.slots[name + ".up"]
+            i = self.slot[name + ".up"]
             x_in = s[name + ".in"]
             grads[i], grads[i + 1] = convT3x3_wgrad(x_in, g_u, out=out(i))
             self._ready(i)
             g = convT3x3_dgrad(g_u, P[i], self.packs, x_in.shape[1:3], mask=x_in)
         if ("mid", 1) in self.bn:
-            g_p, _ = self._stack_bwd_bn(P, self.slots["mid"], "mid", s["mid"], g, grads, out)
+            g_p, _ = self._stack_bwd_bn(P, self.slot["mid"], "mid", s["mid"], g, grads, out)
         else:
-            g_p, _ = self._stack_bwd(P, self.slots["mid"], s["mid"], g, grads, out)
+            g_p, _ = self._stack_bwd(P, self.slot["mid"], s["mid"], g, grads, out)
         for k in range(3, -1, -1):                       # conv4 .. conv1
             g = K.maxpool2_bwd(skips[k], g_p, gskip[k], relu_mask=True, accumulate=True,
                                scale=s.get("pool%d.mask" % (k + 1)))
             name = self.DOWN[k]
             if (name, 1) in self.bn:
-                g_p, _ = self._stack_bwd_bn(P, self.slots[name], name, s[name], g, grads, out, need_dx=k > 0)
+                g_p, _ = self._stack_bwd_bn(P, self.slot[name], name, s[name], g, grads, out, need_dx=k > 0)
             else:
-                g_p, _ = self._stack_bwd(P, self.slots[name], s[name], g, grads, out, need_dx=k > 0)
+                g_p, _ = self._stack_bwd(P, self.slot[name], s[name], g, grads, out, need_dx=k > 0)
         return grads
-
-
-class ResTrunkFunction(torch.autograd.Function):
-    """autograd node: (trunk, save, training, x NCHW, *params) -> logits [B,H,W]."""
-
-    @staticmethod
-    def forward(ctx, trunk, save, training, x, *params):
-        from .trunk import as_nhwc_input
-        xin = as_nhwc_input(x.detach())
-        detached = [p.detach() for p in params]
-        logits, saved = trunk.forward(xin, detached, save, training)
-        ctx.trunk = trunk
-        ctx.saved_acts = saved
-        ctx.params = detached
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        if ctx.saved_acts is None:
-            raise RuntimeError("trunk activations were not saved (forward ran without grad)")
-        grads = ctx.trunk.backward(ctx.saved_acts, dlogits.contiguous(), ctx.params)
-        ctx.saved_acts = None
-        return (None, None, None, None) + tuple(grads)

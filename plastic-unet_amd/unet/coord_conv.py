@@ -15,7 +15,8 @@ Lambda, :149, is the caller's image scaling).  forward() runs punet.trunk's kern
 import torch
 import torch.nn as nn
 
-from .unet_p import double_conv, inconv, down, outconv, _check_gpu_tensor
+from ._plastic import PlasticModel, check_inputs, run_trunk_and_head
+from .unet_p import double_conv, inconv, down, outconv
 
 __all__ = ["CoordConvUNetp"]
 
@@ -34,7 +35,7 @@ class kup(nn.Module):  # coord_conv_script.py:171-192
         self.conv = double_conv(2 * out_ch, out_ch, False)
 
 
-class CoordConvUNetp(nn.Module):
+class CoordConvUNetp(PlasticModel, nn.Module):
     up_first = True      # concat order of the up stages: [upsampled | skip]
 
     def __init__(self, n_channels, n_classes, device, alfa_type='free', rule='hebb', nbf=256, base_ch=8,
@@ -62,61 +63,19 @@ class CoordConvUNetp(nn.Module):
             setattr(self, "up%d" % j, kup(enc[depth - j], enc[depth - 1 - j]))
         self.outc = outconv(base_ch, n_classes)
         self.to(device)
-        self._trunk = None
         print("CoordConv UNet plastic model with plastic rule [%s] initialized" % self.rule)
 
-    def _trunk_plan(self):
-        if self._trunk is None:
-            from punet.trunk import UNetpTrunk
-            self._trunk = UNetpTrunk(self)
-        return self._trunk
+    def _new_trunk(self):
+        from punet.trunk import UNetpTrunk
+        return UNetpTrunk(self)
+
+    def _check_side(self, side):
+        if side % (1 << (self.depth - 1)):
+            raise NotImplementedError("image side %d must be divisible by 2^(depth-1)=%d" % (side, 1 << (self.depth - 1)))
 
     def forward(self, x, hebb):
         single = hebb.dim() == 2
         if single and x.shape[0] != 1:
             raise ValueError("Only batch size: 1 is supported, but was: %d" % x.shape[0])
-        if self.alfa_type not in ("free", "yoked"):
-            raise ValueError("Must select one plasticity coefficient type ('free' or 'yoked')")
-        if self.rule not in ("hebb", "oja"):
-            raise ValueError("Must select one learning rule ('hebb' or 'oja')")
-        _check_gpu_tensor(x, "x")
-        _check_gpu_tensor(hebb, "hebb")
-        if self.n_classes != 1:
-            raise RuntimeError("the plastic head needs n_classes == 1 (activin = x.view(nbf, nbf))")
-        B, C, Hh, Ww = x.shape
-        if C != self.n_channels:
-            raise RuntimeError("expected input with %d channels, got %d" % (self.n_channels, C))
-        if Hh * Ww != self.nbf * self.nbf or Hh != Ww:
-            raise RuntimeError("shape '[%d, %d]' is invalid for input of size %d" % (self.nbf, self.nbf, Hh * Ww))
-        if Hh % (1 << (self.depth - 1)):
-            raise NotImplementedError("image side %d must be divisible by 2^(depth-1)=%d" % (Hh, 1 << (self.depth - 1)))
-        H = hebb.unsqueeze(0) if single else hebb
-        if H.shape != (B, self.nbf, self.nbf):
-            raise ValueError("hebb must be [nbf,nbf] or [B,nbf,nbf]; got %s for batch %d" % (tuple(hebb.shape), B))
-        if x.dtype != torch.float32:
-            x = x.float()
-        from punet.trunk import TrunkFunction
-        from punet.head import PlasticHeadFunction, RULES
-        trunk = self._trunk_plan()
-        trunk.training = self.training
-        params = trunk.params
-        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        from punet.head import fused_head_ok, FusedHeadFunction
-        wo, bo = self.outc.conv.weight, self.outc.conv.bias
-        trunk.fused_head = fused_head_ok(wo.shape[1], self.nbf, False)
-        logits = TrunkFunction.apply(trunk, save, x, *params)
-        if trunk.fused_head:
-            sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha, wo, bo)
-            Y, Hn = FusedHeadFunction.apply(logits, wo, bo, H, self.w, self.alpha, self.eta, RULES[self.rule], True,
-                                            sink, self.trace_grad)
-            return (Y[0], Hn[0]) if single else (Y, Hn)
-        sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha)
-        Y, Hn = PlasticHeadFunction.apply(logits, H, self.w, self.alpha, self.eta, RULES[self.rule], True, sink,
-                                          self.trace_grad)
-        if single:
-            return Y[0], Hn[0]
-        return Y, Hn
-
-    def initialZeroHebb(self, batch=None):
-        shape = (self.nbf, self.nbf) if batch is None else (batch, self.nbf, self.nbf)
-        return torch.zeros(*shape, dtype=torch.float, device=self.torch_dev)
+        x, H = check_inputs(self, x, hebb, single, False)       # no sequential mode
+        return run_trunk_and_head(self, x, hebb, H, single, False)

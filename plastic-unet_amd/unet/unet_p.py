@@ -23,6 +23,8 @@ Extensions (keyword-only in spirit, defaults reproduce the reference):
 import torch
 import torch.nn as nn
 
+from ._plastic import PlasticModel, _check_gpu_tensor, check_inputs, run_trunk_and_head    # noqa: F401
+
 __all__ = ["UNetp", "double_conv", "inconv", "down", "up", "outconv", "unetp_channels"]
 
 
@@ -85,14 +87,7 @@ class outconv(nn.Module):  # unet_p.py:253-260
         self.conv = nn.Conv2d(in_ch, out_ch, 1)
 
 
-def _check_gpu_tensor(t, what):
-    if not (torch.is_tensor(t) and t.is_cuda):
-        raise RuntimeError(
-            "%s must be a tensor on the ROCm device: this UNetp runs only as HIP kernels on MI355X "
-            "(no CPU fallback); got %s" % (what, getattr(t, "device", type(t))))
-
-
-class UNetp(nn.Module):
+class UNetp(PlasticModel, nn.Module):
     def __init__(self, n_channels, n_classes, device, alfa_type='free', rule='hebb', nbf=128, batch_norm=False,
                  bilinear_upsample=False, depth=5, base_ch=8, precision='fp32', hebb_mode='slots', trace_grad=False):
         super().__init__()
@@ -130,14 +125,19 @@ class UNetp(nn.Module):
             setattr(self, "up%d" % j, up(cin, cout, batch_norm=batch_norm, bilinear=bilinear_upsample))
         self.outc = outconv(base_ch, n_classes)
         self.to(device)
-        self._trunk = None
         print("UNet plastic model with plastic rule [%s] initialized" % self.rule)
 
-    def _trunk_plan(self):
-        if self._trunk is None:
-            from punet.trunk import UNetpTrunk
-            self._trunk = UNetpTrunk(self)
-        return self._trunk
+    def _new_trunk(self):
+        from punet.trunk import UNetpTrunk
+        return UNetpTrunk(self)
+
+    def _check_config(self):
+        if (self.batch_norm or self.bilinear_upsample) and self.precision != "fp32":
+            raise NotImplementedError("UNetp(batch_norm=True / bilinear_upsample=True) runs with precision='fp32'")
+
+    def _check_side(self, side):
+        if side % (1 << (self.depth - 1)):
+            raise NotImplementedError("image side %d must be divisible by 2^(depth-1)=%d" % (side, 1 << (self.depth - 1)))
 
     def forward(self, x, hebb):
         single = hebb.dim() == 2
@@ -146,56 +146,5 @@ class UNetp(nn.Module):
             raise ValueError("Only batch size: 1 is supported, but was: %d" % x.shape[0])
         if seq and not single:
             raise ValueError("hebb_mode='sequential' threads one [nbf,nbf] trace through the batch")
-        if self.alfa_type not in ("free", "yoked"):
-            raise ValueError("Must select one plasticity coefficient type ('free' or 'yoked')")
-        if self.rule not in ("hebb", "oja"):
-            raise ValueError("Must select one learning rule ('hebb' or 'oja')")
-        _check_gpu_tensor(x, "x")
-        _check_gpu_tensor(hebb, "hebb")
-        if (self.batch_norm or self.bilinear_upsample) and self.precision != "fp32":
-            raise NotImplementedError("UNetp(batch_norm=True / bilinear_upsample=True) runs with precision='fp32'")
-        if self.n_classes != 1:
-            raise RuntimeError("the plastic head needs n_classes == 1 (activin = x.view(nbf, nbf))")
-        B, C, Hh, Ww = x.shape
-        if C != self.n_channels:
-            raise RuntimeError("expected input with %d channels, got %d" % (self.n_channels, C))
-        if Hh * Ww != self.nbf * self.nbf or Hh != Ww:
-            raise RuntimeError("shape '[%d, %d]' is invalid for input of size %d" % (self.nbf, self.nbf, Hh * Ww))
-        if Hh % (1 << (self.depth - 1)):
-            raise NotImplementedError("image side %d must be divisible by 2^(depth-1)=%d" % (Hh, 1 << (self.depth - 1)))
-        H = hebb.unsqueeze(0) if single else hebb
-        if H.shape != (B if not seq else 1, self.nbf, self.nbf):
-            raise ValueError("hebb must be [nbf,nbf] or [B,nbf,nbf]; got %s for batch %d" % (tuple(hebb.shape), B))
-        if x.dtype != torch.float32:
-            x = x.float()
-
-        from punet.trunk import TrunkFunction
-        from punet.head import PlasticHeadFunction, RULES
-        trunk = self._trunk_plan()
-        trunk.training = self.training      # BatchNorm: per-slot batch statistics vs running statistics
-        params = trunk.params
-        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        from punet.head import fused_head_ok, FusedHeadFunction
-        wo, bo = self.outc.conv.weight, self.outc.conv.bias
-        trunk.fused_head = fused_head_ok(wo.shape[1], self.nbf, seq)
-        logits = TrunkFunction.apply(trunk, save, x, *params)
-        if trunk.fused_head:
-            sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha, wo, bo)
-            Y, Hn = FusedHeadFunction.apply(logits, wo, bo, H, self.w, self.alpha, self.eta, RULES[self.rule], True,
-                                            sink, self.trace_grad)
-            return (Y[0], Hn[0]) if single else (Y, Hn)
-        sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha)
-        if seq:
-            from punet.head import SequentialHeadFunction
-            Y, Hn = SequentialHeadFunction.apply(logits, hebb, self.w, self.alpha, self.eta, RULES[self.rule], sink)
-            return (Y[0], Hn) if B == 1 else (Y, Hn)
-        Y, Hn = PlasticHeadFunction.apply(logits, H, self.w, self.alpha, self.eta, RULES[self.rule], True, sink,
-                                          self.trace_grad)
-        if single:
-            return Y[0], Hn[0]
-        return Y, Hn
-
-    def initialZeroHebb(self, batch=None):
-        """Zero trace [nbf,nbf] (unet_p.py:90-94), or [batch,nbf,nbf] per-slot traces."""
-        shape = (self.nbf, self.nbf) if batch is None else (batch, self.nbf, self.nbf)
-        return torch.zeros(*shape, dtype=torch.float, device=self.torch_dev)
+        x, H = check_inputs(self, x, hebb, single, seq)
+        return run_trunk_and_head(self, x, hebb, H, single, seq)

@@ -9,6 +9,8 @@ hebb is [B,nbf,nbf]; there is no CPU path.
 import torch
 import torch.nn as nn
 
+from ._plastic import PlasticModel, check_inputs, run_trunk_and_head
+
 __all__ = ["UNetpRes"]
 
 
@@ -69,7 +71,7 @@ class up(nn.Module):  # unet_p_res.py:200-220
         self.uconv = nn.Sequential(nn.Dropout2d(p=dropout_ratio, inplace=True), middle(in_ch, out_ch, batch_norm=False))
 
 
-class UNetpRes(nn.Module):
+class UNetpRes(PlasticModel, nn.Module):
     def __init__(self, n_channels, n_classes, device, neurons=16, dropout_ratio=0.5, alfa_type='free', rule='hebb',
                  nbf=128, batch_norm=False, bilinear_upsample=False, hebb_mode='slots', trace_grad=False):
         super().__init__()
@@ -108,14 +110,15 @@ class UNetpRes(nn.Module):
         self.to(device)
         print("UNet plastic model with plastic rule [%s] initialized" % self.rule)
 
-    def _trunk_plan(self):
-        if getattr(self, "_trunk", None) is None:
-            from punet.res_trunk import ResTrunk
-            self._trunk = ResTrunk(self)
-        return self._trunk
+    def _new_trunk(self):
+        from punet.res_trunk import ResTrunk
+        return ResTrunk(self)
+
+    def _check_side(self, side):
+        if side < 16:
+            raise RuntimeError("UNetpRes needs images of at least 16x16 (four 2x2 poolings)")
 
     def forward(self, x, hebb):
-        from .unet_p import _check_gpu_tensor
         single = hebb.dim() == 2
         B, C, Hh, Ww = x.shape
         seq = self.hebb_mode == "sequential"
@@ -125,50 +128,5 @@ class UNetpRes(nn.Module):
             # the reference has no explicit check: activin = x.view(nbf, nbf) fails (S8)
             raise RuntimeError("shape '[%d, %d]' is invalid for input of size %d"
                                % (self.nbf, self.nbf, B * Hh * Ww * self.n_classes))
-        if self.alfa_type not in ("free", "yoked"):
-            raise ValueError("Must select one plasticity coefficient type ('free' or 'yoked')")
-        if self.rule not in ("hebb", "oja"):
-            raise ValueError("Must select one learning rule ('hebb' or 'oja')")
-        _check_gpu_tensor(x, "x")
-        _check_gpu_tensor(hebb, "hebb")
-        if self.n_classes != 1:
-            raise RuntimeError("the plastic head needs n_classes == 1 (activin = x.view(nbf, nbf))")
-        if C != self.n_channels:
-            raise RuntimeError("expected input with %d channels, got %d" % (self.n_channels, C))
-        if Hh * Ww != self.nbf * self.nbf or Hh != Ww:
-            raise RuntimeError("shape '[%d, %d]' is invalid for input of size %d" % (self.nbf, self.nbf, Hh * Ww))
-        if Hh < 16:
-            raise RuntimeError("UNetpRes needs images of at least 16x16 (four 2x2 poolings)")
-        H = hebb.unsqueeze(0) if single else hebb
-        if H.shape != (B if not seq else 1, self.nbf, self.nbf):
-            raise ValueError("hebb must be [nbf,nbf] or [B,nbf,nbf]; got %s for batch %d" % (tuple(hebb.shape), B))
-        if x.dtype != torch.float32:
-            x = x.float()
-        from punet.res_trunk import ResTrunkFunction
-        from punet.head import PlasticHeadFunction, RULES
-        trunk = self._trunk_plan()
-        params = trunk.params
-        save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        from punet.head import fused_head_ok, FusedHeadFunction
-        wo, bo = self.outc.conv.weight, self.outc.conv.bias
-        trunk.fused_head = fused_head_ok(wo.shape[1], self.nbf, seq)
-        logits = ResTrunkFunction.apply(trunk, save, self.training, x, *params)
-        if trunk.fused_head:
-            sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha, wo, bo)
-            Y, Hn = FusedHeadFunction.apply(logits, wo, bo, H, self.w, self.alpha, self.eta, RULES[self.rule], True,
-                                            sink, self.trace_grad)
-            return (Y[0], Hn[0]) if single else (Y, Hn)
-        sink = None if trunk.gradbuf is None else (trunk.gradbuf, self.w, self.alpha)
-        if seq:
-            from punet.head import SequentialHeadFunction
-            Y, Hn = SequentialHeadFunction.apply(logits, hebb, self.w, self.alpha, self.eta, RULES[self.rule], sink)
-            return (Y[0], Hn) if B == 1 else (Y, Hn)
-        Y, Hn = PlasticHeadFunction.apply(logits, H, self.w, self.alpha, self.eta, RULES[self.rule], True, sink,
-                                          self.trace_grad)
-        if single:
-            return Y[0], Hn[0]
-        return Y, Hn
-
-    def initialZeroHebb(self, batch=None):
-        shape = (self.nbf, self.nbf) if batch is None else (batch, self.nbf, self.nbf)
-        return torch.zeros(*shape, dtype=torch.float, device=self.torch_dev)
+        x, H = check_inputs(self, x, hebb, single, seq)
+        return run_trunk_and_head(self, x, hebb, H, single, seq)

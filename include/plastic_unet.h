@@ -28,6 +28,8 @@
  *                                                      src/eval.py:20-64,66-103
  *   pu_rle_encode      mask > threshold and rle_encode of every test image
  *                                                      src/infer.py:59-65, src/utils/rle_encode.py:6-17
+ *   pu_lovasz_fwd/bwd  the Lovasz extension of the Jaccard loss on probabilities, per image (no reference
+ *                      call site: an extension, the surrogate of the IoU that validation reports)
  *   pu_adam_multi     torch.optim.Adam.step           src/train.py:66,111
  *   pu_grad_norm       torch.nn.utils.clip_grad_norm_ (no reference call site: an extension for
  *   pu_adam_multi_clipped  episode training) - the norm and coefficient, and Adam on the scaled g
@@ -524,6 +526,36 @@ int pu_seg_metrics(const float* y, const float* t, int batch, long long n, const
 size_t pu_rle_encode_workspace_bytes(int batch, int h, int w);
 int pu_rle_encode(const float* y, int batch, int h, int w, double threshold, int* offsets, int* runs, long long cap,
                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Lovasz loss on probabilities: the Lovasz extension of the Jaccard loss (Berman et al.,
+ * lovasz_softmax for the one foreground class), per image, mean over the batch.  y and t are
+ * [batch][n], contiguous.  For image b:
+ *   1. fg_i = 1 when 0.5 <= t_i <= 1, else 0 (the foreground of pu_seg_metrics)
+ *   2. e_i = fg_i ? 1.0f - y_i : y_i, one fp32 rounding
+ *   3. the pixels are ranked by e descending, pixels of equal e (-0 equals +0) by pixel index ascending:
+ *      a total order
+ *   4. G = sum fg; at rank k (0-based) cf_k and cb_k count the foreground and background pixels among
+ *      the ranks 0..k;  J_k = 1 - (G - cf_k) / (G + cb_k),  J_-1 = 0,  g_k = J_k - J_k-1, in fp64 from the
+ *      integer counts, not contracted: one division and two subtractions per rank.  The denominator is
+ *      never 0 (G = 0 leaves cb_k >= 1), and an empty mask gives loss_b = max_i y_i without a special case
+ *   5. loss_b = sum_k (double)e_(k) * g_k in one fixed order, rounded to fp32 once -> loss_per_image[b]
+ *      (may be NULL);  loss[0] = (sum_b loss_b) / batch, in fp64 in image order, rounded once
+ *   6. dtab[b][i] = (float)(fg_i ? -g_rank(i) : +g_rank(i)): d loss_b / d y_i (may be NULL: the loss alone)
+ * pu_lovasz_bwd: dy[b][i] = dtab[b][i] * (g / (float)batch), g = *grad_loss (device scalar; NULL: 1): one
+ * fp32 division per call, one fp32 multiply per element.
+ * The loss does not depend on how equal e are ordered; dtab does, and rule 3 fixes it.  A non-finite y
+ * gives an unspecified result but no out-of-range access: every address comes from a pixel index.
+ * One workgroup per image sorts its keys in LDS, so 1 <= n <= 16384 (128^2); a larger n is
+ * PU_ERR_UNSUPPORTED.  1 <= batch <= 65535.  y, t, loss, loss_per_image, dtab and dy are 4-byte aligned.
+ * The workspace (8-byte aligned) holds one double per image: batch * 8 bytes; the query gives 0 for a
+ * shape the entry rejects.  No atomics (the same bits on every call) and no host synchronisation:
+ * graph-capturable.  Forward: two launches; backward: one.
+ * ------------------------------------------------------------------------------------------- */
+size_t pu_lovasz_workspace_bytes(int batch, int n);
+int pu_lovasz_fwd(const float* y, const float* t, int batch, int n, float* loss, float* loss_per_image, float* dtab,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int pu_lovasz_bwd(const float* dtab, const float* grad_loss, int batch, int n, float* dy, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-tensor Adam (torch.optim.Adam, amsgrad=False, maximize=False):

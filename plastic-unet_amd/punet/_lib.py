@@ -141,6 +141,9 @@ SIGNATURES = [
     ("pu_seg_metrics", c_int, [P, P, c_int, c_ll, ctypes.POINTER(c_double), c_int, P, P, P, c_size, P]),
     ("pu_rle_encode_workspace_bytes", c_size, [c_int, c_int, c_int]),
     ("pu_rle_encode", c_int, [P, c_int, c_int, c_int, c_double, P, P, c_ll, P, c_size, P]),
+    ("pu_lovasz_workspace_bytes", c_size, [c_int, c_int]),
+    ("pu_lovasz_fwd", c_int, [P, P, c_int, c_int, P, P, P, P, c_size, P]),
+    ("pu_lovasz_bwd", c_int, [P, P, c_int, c_int, P, P]),
     ("pu_bn_workspace_bytes", c_size, [c_int, c_ll, c_int]),
     ("pu_bn_fwd", c_int, [P, P, P, P, P, P, P, P, c_int, c_ll, c_int, c_float, c_float, c_int, c_int, P, P, c_size, P]),
     ("pu_bn_bwd", c_int, [P, P, P, P, P, P, P, P, c_int, c_ll, c_int, P, P, P, c_size, P]),

@@ -14,25 +14,49 @@ Batched semantics: slot b of step s carries its trace to 
 s+1; loss = mean BCE over all slots' pixels (so each slot contributes the reference's per-sample
 gradient / B).  Under data parallelism each rank runs its own slots (the global batch is sharded
 contiguously by rank) and gradients are averaged across ranks; traces stay per rank.
+
+Trainer(loss="lovasz" | "bce+lovasz") trains on the per-image Lovasz loss, mean over the slots,
+alone or added to the BCE (select_loss); the default, "bce", is the reference's.
 """
 import torch
 import torch.distributed as dist
 
 from . import dp
-from .head import bce_loss
+from .head import bce_loss, lovasz_loss
 from .optim import FusedAdam
+
+
+LOSSES = ("bce", "lovasz", "bce+lovasz")
+
+
+def select_loss(loss="bce", lovasz_weight=1.0):
+    """The function (y, t) -> loss a Trainer optimises: "bce" is bce_loss itself, "lovasz" lovasz_loss
+    itself (per image, mean over the slots), "bce+lovasz" bce + lovasz_weight * lovasz, composed by
+    autograd: each loss writes its own dy and autograd adds them."""
+    if loss == "bce":
+        return bce_loss
+    if loss == "lovasz":
+        return lovasz_loss
+    if loss == "bce+lovasz":
+        w = float(lovasz_weight)
+        return lambda y, t: bce_loss(y, t) + w * lovasz_loss(y, t)
+    raise ValueError("loss must be one of %s, not %r" % (", ".join(repr(k) for k in LOSSES), loss))
 
 
 class Trainer:
     def __init__(self, net, lr=3e-4, steplr=1e5, gamma=0.666, betas=(0.9, 0.999), eps=1e-8,
                  flat_grads=True, bucket_mb=16, overlap=True, force_reduce=False, graph=False,
-                 max_grad_norm=None):
-        """max_grad_norm: clip the gradients by their global 2-norm inside the Adam step (FusedAdam's
+                 max_grad_norm=None, loss="bce", lovasz_weight=1.0):
+        """loss: what every kind of step optimises and returns - "bce" (the reference's), "lovasz" or
+        "bce+lovasz" (bce + lovasz_weight * lovasz), see select_loss.
+        max_grad_norm: clip the gradients by their global 2-norm inside the Adam step (FusedAdam's
         max_grad_norm: .grad stays unscaled); every kind of step then leaves its norm, before
         clipping, in last_grad_norm.  Under data parallelism the norm is taken after the all-reduce.
         force_reduce: run the overlapped all-reduce path even in a world of one rank (tests the
         RCCL async path on a one-GPU box; an AVG over one rank is the identity)"""
         self.net = net
+        self.loss_name = loss
+        self.loss_fn = select_loss(loss, lovasz_weight)
         self.params = list(net.parameters())
         self.opt = FusedAdam(net.parameters(), lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm)
         self.sched = torch.optim.lr_scheduler.StepLR(self.opt, gamma=gamma, step_size=int(steplr))
@@ -144,7 +168,7 @@ class Trainer:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 y, hn = self.net(self._sx, self._sh)
-                loss = bce_loss(y, self._st)
+                loss = self.loss_fn(y, self._st)
                 loss.backward()
             self._graph = g
             self._gloss, self._ghn = loss.detach(), hn.detach()
@@ -190,7 +214,7 @@ class Trainer:
             losses = []
             for k in range(len(xs)):
                 y, h = self.net(xs[k], h)
-                losses.append(bce_loss(y, ts[k]))
+                losses.append(self.loss_fn(y, ts[k]))
             (torch.stack(losses).sum() / len(losses)).backward()
         finally:
             if trunk is not None:
@@ -205,7 +229,7 @@ class Trainer:
         for p in self.params:
             p.grad = None
         y, hn = self.net(x, hebb.detach())
-        loss = bce_loss(y, t)
+        loss = self.loss_fn(y, t)
         if self.reducer is not None:
             self.reducer.begin()          # buckets all-reduce (async) as the backward completes them
         loss.backward()

@@ -1,7 +1,8 @@
 """autograd nodes for the plastic head and BCELoss, each a pair of HIP kernel launches.
 
 Reference: yaricom/Plastic-UNet src/unet/unet_p.py:69-88 (head) and src/train.py:70,101-105
-(nn.BCELoss); backward = what loss.backward() (train.py:110) computes for them.
+(nn.BCELoss); backward = what loss.backward() (train.py:110) computes for them.  The Lovasz loss
+(LovaszLossFunction, lovasz_loss, LovaszLoss) has no call site in the reference: an extension.
 """
 import torch
 import torch.nn as nn
@@ -221,3 +222,40 @@ class BCELoss(nn.Module):
 
     def forward(self, input, target):
         return bce_loss(input, target)
+
+
+class LovaszLossFunction(torch.autograd.Function):
+    """(y [B, n], t [B, n]) -> the mean over the images of the Lovasz loss of each (pu_lovasz_fwd).  The
+    forward sorts every image once and keeps D = d loss_b / d y; the backward is D * (g / B)."""
+
+    @staticmethod
+    def forward(ctx, y, t):
+        y = y.contiguous()
+        t = t.detach().contiguous()
+        loss, _, dtab = K.lovasz_fwd(y, t)
+        ctx.save_for_backward(dtab)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dtab, = ctx.saved_tensors
+        return K.lovasz_bwd(dtab, g), None
+
+
+def lovasz_loss(y, t):
+    """Lovasz extension of the Jaccard loss on probabilities (Berman's lovasz_softmax for the one
+    foreground class), per image, mean over the batch: y and t [B, n] or [B, H, W], n <= 16384.  A pixel
+    is foreground when 0.5 <= t <= 1, as validation reads it."""
+    if y.dim() < 2:
+        raise ValueError("lovasz_loss: y needs a leading batch axis, [B, n] or [B, H, W] (got shape %s)" % (tuple(y.shape),))
+    if t.numel() != y.numel():
+        raise ValueError("Target size (%s) must be the same as input size (%s)" % (tuple(t.shape), tuple(y.shape)))
+    B = y.shape[0]
+    return LovaszLossFunction.apply(y.reshape(B, -1), t.reshape(B, -1))
+
+
+class LovaszLoss(nn.Module):
+    """``lovasz_loss`` as a module, next to BCELoss."""
+
+    def forward(self, input, target):
+        return lovasz_loss(input, target)

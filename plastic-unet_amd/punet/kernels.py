@@ -17,7 +17,7 @@ from ._lib import (ConvArgs, WgradArgs, PlasticArgs, PlasticHeadArgs, PlasticBwd
 
 __all__ = ["KernelProfiler", "igemm", "wgrad", "pack_weight", "nchw_to_nhwc", "maxpool2_fwd", "maxpool2_bwd",
            "outconv_fwd", "outconv_bwd", "plastic_fwd", "trace_update", "plastic_bwd", "plastic_bwd_trace", "bce_fwd",
-           "bce_bwd", "seg_metrics", "rle_encode", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
+           "bce_bwd", "seg_metrics", "rle_encode", "lovasz_fwd", "lovasz_bwd", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
 
 
 def lib():
@@ -751,6 +751,49 @@ def rle_encode(y, threshold, cap=None):
         check(L.pu_rle_encode(y.data_ptr(), B, H, W, float(threshold), offsets.data_ptr(), runs.data_ptr() or None, cap,
                               ws.data_ptr(), nbytes, _stream()), "pu_rle_encode")
     return offsets, runs
+
+
+LOVASZ_MAX_N = 16384    # pixels per image one workgroup sorts in LDS (csrc/lovasz.hip)
+
+
+def lovasz_fwd(y, t):
+    """Lovasz loss on probabilities, per image (pu_lovasz_fwd): y and t [B, n] -> (loss 0-d, loss_per_image
+    [B], D [B, n]) on the device.  loss is the mean of the image losses; D[b][i] is d loss_b / d y[b][i],
+    the table lovasz_bwd scales - see plastic_unet.h for the order of the sort and of every sum."""
+    _req(y, "y"); _req(t, "t")
+    if y.dim() != 2 or y.numel() == 0:
+        raise ValueError("lovasz_fwd: y must be [B, n] with no empty axis (got shape %s)" % (tuple(y.shape),))
+    if t.shape != y.shape:
+        raise ValueError("Target size (%s) must be the same as input size (%s)" % (tuple(t.shape), tuple(y.shape)))
+    B, n = y.shape
+    if n > LOVASZ_MAX_N:
+        raise ValueError("lovasz_fwd: %d pixels per image; one workgroup sorts an image in LDS, up to %d (128 x 128)"
+                         % (n, LOVASZ_MAX_N))
+    L = lib()
+    nbytes = L.pu_lovasz_workspace_bytes(B, n)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=y.device)
+    loss = torch.empty((), dtype=torch.float32, device=y.device)
+    per_image = torch.empty(B, dtype=torch.float32, device=y.device)
+    dtab = torch.empty_like(y)
+    with _Rec("lovasz_fwd", nbytes=12.0 * y.numel()):
+        check(L.pu_lovasz_fwd(y.data_ptr(), t.data_ptr(), B, n, loss.data_ptr(), per_image.data_ptr(), dtab.data_ptr(),
+                              ws.data_ptr(), nbytes, _stream()), "pu_lovasz_fwd")
+    return loss, per_image, dtab
+
+
+def lovasz_bwd(dtab, grad_loss):
+    """dy = D * (grad_loss / B) (pu_lovasz_bwd): D [B, n] from lovasz_fwd, grad_loss a device scalar
+    (None: 1)."""
+    _req(dtab, "dtab")
+    if dtab.dim() != 2 or dtab.numel() == 0:
+        raise ValueError("lovasz_bwd: dtab must be [B, n] with no empty axis (got shape %s)" % (tuple(dtab.shape),))
+    g = grad_loss.contiguous() if grad_loss is not None else None
+    _req(g, "grad_loss")
+    dy = torch.empty_like(dtab)
+    B, n = dtab.shape
+    with _Rec("lovasz_bwd", nbytes=8.0 * dtab.numel()):
+        check(lib().pu_lovasz_bwd(dtab.data_ptr(), _p(g), B, n, dy.data_ptr(), _stream()), "pu_lovasz_bwd")
+    return dy
 
 
 def grad_norm(grads, max_norm):

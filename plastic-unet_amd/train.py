@@ -13,6 +13,8 @@ save checkpoints (:153-203).  Differences, all opt-in:
                    through the K trace updates (truncated BPTT), one Adam step per episode; eta learns
   --clip-grad X    clip the gradients of every step to the global 2-norm X, on the device inside the
                    Adam step; the per-step norms are logged as train/grad_norms (0: off)
+  --loss NAME      bce (default, the reference) | lovasz | bce+lovasz (bce + --lovasz-weight * lovasz): the
+                   training loss, which is also the one logged; validation stays BCE and accuracy
   --resident       keep the whole training set in HBM; default: batches stream host -> HBM through
                    pinned, double-buffered asynchronous copies (punet/loader.py) under the previous step
 Data-parallel training: launch with torch.distributed.run; each rank trains its contiguous shard
@@ -74,7 +76,8 @@ def train(net, X_train, X_val, y_train, y_val, params):
     samples_count = len(X_train)
     loss_between_saves, last_save_epoch = 0.0, 0
     trainer = Trainer(net, lr=params["lr"], steplr=params["steplr"], gamma=params["gamma"],
-                      max_grad_norm=clip_grad if clip_grad > 0 else None)
+                      max_grad_norm=clip_grad if clip_grad > 0 else None, loss=params.get("loss", "bce"),
+                      lovasz_weight=float(params.get("lovasz_weight", 1.0)))
     ranges = list(_batches(samples_count, bs, world, rank))
     if params.get("prefetch", True):
         # stream batches host -> HBM (pinned, double-buffered, overlapping the previous step)
@@ -188,7 +191,8 @@ def start_train(x_train, x_valid, y_train, y_valid, out_dir, model, img_width, i
                 max_train_time=-1, load=False, gpu=True, epochs=5, lr=3e-5, val_ratio=0.05, val_every=50,
                 save_every=100, gamma=0.666, steplr=1e6, rollout=50000, prule="hebb", debug=False,
                 model_type="unetpres", depth=5, base_ch=8, neurons=16, batch_size=1, hebb_mode="slots",
-                batch_norm=False, bilinear_upsample=False, prefetch=True, bptt=0, clip_grad=0.0):
+                batch_norm=False, bilinear_upsample=False, prefetch=True, bptt=0, clip_grad=0.0, loss="bce",
+                lovasz_weight=1.0):
     world, rank, local = dp.init_from_env()
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
@@ -197,7 +201,7 @@ def start_train(x_train, x_valid, y_train, y_valid, out_dir, model, img_width, i
               "val_ratio": val_ratio, "val_every": val_every, "save_every": save_every, "rollout": rollout,
               "gamma": gamma, "steplr": steplr, "prule": prule, "im_width": img_width, "im_height": img_height,
               "im_chan": img_chan, "debug": debug, "batch_size": batch_size, "prefetch": prefetch,
-              "bptt": bptt, "clip_grad": clip_grad}
+              "bptt": bptt, "clip_grad": clip_grad, "loss": loss, "lovasz_weight": lovasz_weight}
     if model_type == "unetp":
         net = UNetp(n_channels=img_chan, n_classes=1, nbf=img_width, batch_norm=batch_norm,
                     bilinear_upsample=bilinear_upsample, device=device, rule=prule, depth=depth, base_ch=base_ch,
@@ -257,6 +261,11 @@ def parse_args(argv=None):
     parser.add_option('--clip-grad', dest='clip_grad', type='float', default=0.0,
                       help='X > 0: clip the gradients of every step to the global 2-norm X (device-side, fused '
                            'into the Adam step) and log the per-step norms; 0: off')
+    parser.add_option('--loss', dest='loss', default='bce', choices=['bce', 'lovasz', 'bce+lovasz'],
+                      help='the training loss: bce (the reference), lovasz (the Lovasz extension of the Jaccard loss '
+                           'on probabilities, per image, up to 128 x 128) or bce+lovasz; validation stays BCE')
+    parser.add_option('--lovasz-weight', dest='lovasz_weight', type='float', default=1.0,
+                      help='w of --loss bce+lovasz: bce + w * lovasz')
     parser.add_option('--seed', dest='seed', type='int', default=0)
     parser.add_option('--resident', dest='resident', action='store_true', default=False,
                       help='copy the whole training set to HBM once instead of streaming batches')
@@ -295,4 +304,4 @@ if __name__ == '__main__':
                 debug=args.debug, model_type=args.model_type, depth=args.depth, base_ch=args.base_ch,
                 neurons=args.neurons, batch_size=args.batch_size, hebb_mode=args.hebb_mode,
                 batch_norm=args.batch_norm, bilinear_upsample=args.bilinear, prefetch=not args.resident,
-                bptt=args.bptt, clip_grad=args.clip_grad)
+                bptt=args.bptt, clip_grad=args.clip_grad, loss=args.loss, lovasz_weight=args.lovasz_weight)

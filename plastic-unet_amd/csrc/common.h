@@ -149,23 +149,34 @@ __device__ __forceinline__ void static_for(F&& f) {
 // descriptor's range, so the range check writes zeros into LDS (probed: tools/probes/oob_lds.hip)
 constexpr unsigned LEAN_OOB = 0x80000000u;
 
-// vector and address-space types of the MFMA kernels (igemm.hip, igemm_bf16.hip, wgrad.hip, ...)
+// vector and address-space types (those of the MFMA kernels alone: mfma_common.h)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void gbl_void_t;
 
-// buffer_load_dwordx4 ... lds of 16 B per lane through a descriptor built from wave-uniform
-// inputs, made provably uniform (no waterfall loops around the loads); bytes == 0 drops every
-// lane (zeros land in LDS).  Kept out of the kernel template so the host pass never sees the
-// descriptor type.
-__device__ __forceinline__ void lean_load(const void* base, unsigned bytes, void* lds_dst, unsigned voff, unsigned soff) {
-    const unsigned long long b = (unsigned long long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    void* ub = (void*)(((unsigned long long)hi << 32) | lo);
-    __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(ub, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t*)lds_dst, 16, voff, __builtin_amdgcn_readfirstlane(soff), 0, 0);
+// 4 consecutive activation elements as fp32: fp32 as they are; bf16 widened, and rounded once (to
+// nearest even) at the store
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 ld4(const __bf16* p) {
+    const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(p);
+    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+}
+__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+__device__ __forceinline__ void st4(__bf16* p, f32x4 v) {
+    bf16x4_t o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (__bf16)v[e];
+    *reinterpret_cast<bf16x4_t*>(p) = o;
+}
+
+// blocks of a grid-stride launch over `total` items
+inline int grid_for(long long total, int block = 256, int cap = 8192) {
+    long long g = (total + block - 1) / block;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
 }
 
 }  // namespace pu

@@ -12,18 +12,12 @@
 //   * the split-K partial-tile store and the split-K finish;
 //   * the host side of both entry points: ConvPlan, the argument rules they share
 //     (conv_check_args) and the parameter fill (conv_fill_params);
-//   * the exact 3-term bf16 split of fp32 operands (pairs form).
+//   * through mfma_common.h: the vector types, the exact 3-term bf16 split of fp32 operands
+//     (pairs form), the six-product sequence and the LDS barrier.
 #pragma once
-#include "common.h"
+#include "mfma_common.h"
 
 namespace pu {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 // The fields both paths use.  T: the element type of activations, weights, masks and the residual
 // in HBM (the bias and the split-K partials are fp32 on both paths).
@@ -63,21 +57,6 @@ struct IgemmParams : ConvParams<float> {
 struct IgemmBf16Params : ConvParams<__bf16> {
     static constexpr bool kF32Epi = false;
 };
-
-// 4 consecutive elements as fp32: fp32 as they are; bf16 widened, and rounded once (to nearest
-// even) at the store
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 ld4(const __bf16* p) {
-    const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(p);
-    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ void st4(__bf16* p, f32x4 v) {
-    bf16x4_t o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (__bf16)v[e];
-    *reinterpret_cast<bf16x4_t*>(p) = o;
-}
 
 // Output position of GEMM row m: the pixel itself, or (SHUFFLE2) the batch row base b*shuf_h and
 // the top-left corner (2ho - off, 2wo - off) of its 2x2 output block; b = the image (formed only
@@ -416,34 +395,6 @@ inline void conv_fill_params(const pu_conv_args* a, long long M, P* pp) {
     p.dTaps = make_fastdiv(p.taps);
     p.cgroup = a->cgroup;
     p.in_pix = a->batch * a->in_h * a->in_w;
-}
-
-__device__ __forceinline__ unsigned pk_bf16(f32x2 v) {
-    const bf16x2_t h = __builtin_convertvector(v, bf16x2_t);
-    return __builtin_bit_cast(unsigned, h);
-}
-
-// x = hi + mid + lo exactly (round-to-nearest at each step), 8 elements as 4 pairs
-__device__ __forceinline__ void split3_pairs(const f32x4 lo4, const f32x4 hi4, bf16x8_t& h, bf16x8_t& m, bf16x8_t& l) {
-#pragma clang fp contract(off)
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 hv, mv, lv;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x2 x = q < 2 ? f32x2{lo4[2 * q], lo4[2 * q + 1]} : f32x2{hi4[2 * q - 4], hi4[2 * q - 3]};
-        const unsigned a = pk_bf16(x);
-        const f32x2 af = {__builtin_bit_cast(float, a << 16), __builtin_bit_cast(float, a & 0xffff0000u)};
-        const f32x2 r = x - af;
-        const unsigned b = pk_bf16(r);
-        const f32x2 bf = {__builtin_bit_cast(float, b << 16), __builtin_bit_cast(float, b & 0xffff0000u)};
-        const f32x2 c = r - bf;
-        hv[q] = a;
-        mv[q] = b;
-        lv[q] = pk_bf16(c);
-    }
-    h = __builtin_bit_cast(bf16x8_t, hv);
-    m = __builtin_bit_cast(bf16x8_t, mv);
-    l = __builtin_bit_cast(bf16x8_t, lv);
 }
 
 // Winograd F(2x2,3x3) path (winograd.hip), dispatched from pu_conv_igemm

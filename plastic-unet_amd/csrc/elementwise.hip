@@ -11,21 +11,8 @@
 
 namespace pu {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-// activation element access for the fp32 and bf16 (config C3) variants: compute is fp32
-template <typename T> __device__ __forceinline__ f32x4 ld4(const T* p);
-template <> __device__ __forceinline__ f32x4 ld4<float>(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-template <> __device__ __forceinline__ f32x4 ld4<__bf16>(const __bf16* p) {
-    const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
-    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
-template <typename T> __device__ __forceinline__ void st4(T* p, f32x4 v);
-template <> __device__ __forceinline__ void st4<float>(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-template <> __device__ __forceinline__ void st4<__bf16>(__bf16* p, f32x4 v) {
-    *reinterpret_cast<bf16x4*>(p) = bf16x4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-}
+// activation element access for the fp32 and bf16 (config C3) variants is common.h's ld4 / st4:
+// compute is fp32
 
 // K position -> tap-major index (tap*C + c) for a channel-group-major packed K axis
 __device__ __forceinline__ int ungroup_k(int k, int C, int taps, int G) {
@@ -731,13 +718,6 @@ __global__ void colsum_final_kernel(const double* __restrict__ part, int nparts,
 static int colsum_blocks(long long rows) {
     long long b = (rows + 1023) / 1024;
     return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
-
-static int grid_for(long long total, int block = 256, int cap = 8192) {
-    long long g = (total + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 __global__ void f32_to_bf16_kernel(const float* __restrict__ x, __bf16* __restrict__ y, long long n4) {

@@ -653,14 +653,7 @@ __global__ __launch_bounds__(NW * 64) void igemm_x6_kernel(const IgemmParams p) 
             split3_bf16(xa[i], xb[i], xh, xm, xl);
 #pragma unroll
             for (int j = 0; j < FN; ++j) {
-                f32x16 c = acc[i][j];
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[1][j], xm, c, 0, 0, 0);   // small terms first
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[2][j], xh, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[0][j], xl, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[1][j], xh, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[0][j], xm, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[0][j], xh, c, 0, 0, 0);
-                acc[i][j] = c;
+                acc[i][j] = mma6(fw[0][j], fw[1][j], fw[2][j], xh, xm, xl, acc[i][j]);
             }
             if (i == 0) issue(ts + NBUF - 1, (ts + NBUF - 1) % NBUF);
         }
@@ -840,14 +833,7 @@ __global__ __launch_bounds__(NW * 64) void igemm_x6_lean_kernel(const IgemmParam
                 split3_pairs(xa[i], xb[i], xh, xm, xl);
 #pragma unroll
                 for (int j = 0; j < FN; ++j) {
-                    f32x16 c = acc[i][j];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[1][j], xm, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[2][j], xh, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[0][j], xl, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[1][j], xh, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[0][j], xm, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[0][j], xh, c, 0, 0, 0);
-                    acc[i][j] = c;
+                    acc[i][j] = mma6(fw[0][j], fw[1][j], fw[2][j], xh, xm, xl, acc[i][j]);
                 }
                 if (i == 0) {
                     if constexpr (u + 2 < SPG) issue(g, std::integral_constant<int, u + 2>{});

@@ -534,9 +534,7 @@ __global__ __launch_bounds__(HB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
                 setup(next);                          // this group's MFMAs and the epilogue
                 load(0, (next % p.gn) * HB_BN);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            lds_barrier();
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int toff = ((t / 3) * HW + (t % 3)) * HB_PX;

@@ -17,8 +17,6 @@
 
 namespace pu {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BN_SPLITS_MAX = 64;
 
 // per-(split, slot, channel) partial sums over the split's pixel range:

@@ -16,8 +16,6 @@
 
 namespace pu {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int HK = 16;   // k chunk staged through LDS
 
 // Tile T x T per 256-thread block (T = 64: 4x4 per thread; T = 32: 2x2, for grids that would not
@@ -195,16 +193,6 @@ inline int fused_head_chunk(int N) {
     return best;
 }
 
-template <typename T>
-__device__ __forceinline__ f32x4 fh_ld4(const T* p);
-template <>
-__device__ __forceinline__ f32x4 fh_ld4<float>(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-template <>
-__device__ __forceinline__ f32x4 fh_ld4<__bf16>(const __bf16* p) {
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-    const b4 v = *reinterpret_cast<const b4*>(p);
-    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
 // the pipelined head's feature stream: every feature is read once (row 0 aside), so the
 // nontemporal form (PU_HP_NT=1) keeps it from displacing H / w / alpha in the caches
 #ifndef PU_HP_NT
@@ -213,7 +201,7 @@ __device__ __forceinline__ f32x4 fh_ld4<__bf16>(const __bf16* p) {
 template <typename T>
 __device__ __forceinline__ f32x4 fh_ld4s(const T* p) {
     if constexpr (PU_HP_NT && sizeof(T) == 4) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-    return fh_ld4<T>(p);
+    return ld4(p);
 }
 
 template <typename T, int L, int TPW, int R = FH_R>
@@ -272,7 +260,7 @@ __global__ __launch_bounds__(FH_NT) void head_fused_fwd_kernel(const T* __restri
                 const f32x4 ww = *reinterpret_cast<const f32x4*>(wo + c);
                 f32x4 v[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) v[u] = fh_ld4<T>(px[u] + c);
+                for (int u = 0; u < U; ++u) v[u] = ld4(px[u] + c);
 #pragma unroll
                 for (int u = 0; u < U; ++u) sacc[u] += dot4_fma(v[u], ww);
             }
@@ -504,7 +492,7 @@ __global__ __launch_bounds__(HP_NT) void head_pipe_fwd_kernel(const T* __restric
                     const int r = qc / N, col = (qc + rot) & (N - 1);
                     const T* px = fb + ((long long)(r == 0 ? 0 : i0 + r - 1) * N + col) * C;
                     for (int c = lane * 4 + 4 * L; c < C; c += 4 * L)
-                        sacc += dot4_fma(fh_ld4<T>(px + c), *reinterpret_cast<const f32x4*>(wo + c));
+                        sacc += dot4_fma(ld4(px + c), *reinterpret_cast<const f32x4*>(wo + c));
                 }
                 float t = sacc;
                 t += __shfl_xor(t, 8, 16);
@@ -992,13 +980,6 @@ __global__ void bce_bwd_kernel(const float* __restrict__ y, const float* __restr
         const float d = gg * (yy - tt) / fmaxf((1.f - yy) * yy, 1e-12f);
         dy[i] = d / inv_n;
     }
-}
-
-static int grid_for(long long total, int block = 256, int cap = 8192) {
-    long long g = (total + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 // 64-tiles when they give >= 2 blocks per CU, else 32-tiles (bs 32 x 128^2: 512 blocks)

@@ -50,14 +50,6 @@ struct WinoParams {
     unsigned u_bytes;     // extent of U
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    void* ub = (void*)(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(ub, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-
 // epilogue operand load / store through a buffer descriptor (out-of-range offsets: zeros / dropped)
 __device__ __forceinline__ f32x4 epi_ld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
@@ -414,9 +406,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if constexpr (VA == 3) make_v(std::integral_constant<int, 2>{}, (unsigned)(2 * VS));
     load_row(kc0 + 1, 0);
     if constexpr (VA == 3) load_row(kc0 + 1, 2);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    lds_barrier();
     read_v(0u, I0{});
     W4S(1);
 
@@ -435,9 +425,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         sub(kc, std::integral_constant<int, 3>{}, BF{});
     }
     // every wave is done reading the V ring (the exchange reuses it)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    lds_barrier();
     W4S(2);
 
     // ---- output transform.  Column sums s_py[j] (lane-local, summed in this order):
@@ -499,9 +487,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         send(std::integral_constant<int, 2>{});
         asm volatile("" ::: "memory");
         send(std::integral_constant<int, 3>{});
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        lds_barrier();
         recv(std::integral_constant<int, 1>{});
         asm volatile("" ::: "memory");
         recv(std::integral_constant<int, 2>{});
@@ -517,18 +503,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 xs[e * 64 + lane] = W4A(0, SB)[e] + W4A(1, SB)[e] + W4A(2, SB)[e];
                 xs[(16 + e) * 64 + lane] = W4A(1, SB)[e] - W4A(2, SB)[e] - W4A(3, SB)[e];
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            lds_barrier();
             const float* xr = xch + FROM * (2 * 16 * 64);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 W4A(0, SB)[e] = xr[e * 64 + lane];
                 W4A(1, SB)[e] = xr[(16 + e) * 64 + lane];
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            lds_barrier();
         };
         round(std::integral_constant<int, 1>{});
         round(std::integral_constant<int, 2>{});

@@ -30,6 +30,8 @@
  *                                                      src/infer.py:59-65, src/utils/rle_encode.py:6-17
  *   pu_lovasz_fwd/bwd  the Lovasz extension of the Jaccard loss on probabilities, per image (no reference
  *                      call site: an extension, the surrogate of the IoU that validation reports)
+ *   pu_augment         random flips and reflected shifts of a training batch, images and masks alike (no
+ *   pu_flip_mean       reference call site: extensions) - and the mean of a prediction with its mirror's
  *   pu_adam_multi     torch.optim.Adam.step           src/train.py:66,111
  *   pu_grad_norm       torch.nn.utils.clip_grad_norm_ (no reference call site: an extension for
  *   pu_adam_multi_clipped  episode training) - the norm and coefficient, and Adam on the scaled g
@@ -556,6 +558,33 @@ size_t pu_lovasz_workspace_bytes(int batch, int n);
 int pu_lovasz_fwd(const float* y, const float* t, int batch, int n, float* loss, float* loss_per_image, float* dtab,
                   void* workspace, size_t workspace_bytes, void* stream);
 int pu_lovasz_bwd(const float* dtab, const float* grad_loss, int batch, int n, float* dy, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training augmentation and flip-averaged inference (no reference call site: extensions).
+ * pu_augment: x [batch][cx][h][w] and t [batch][ct][h][w] (fp32 NCHW, contiguous: the arrays train.py hands
+ * the net) -> x_out, t_out of the same shapes.  table: DEVICE int32 [batch][4], row b = {flip, dy, dx, 0}.
+ * Every plane of slot b, image and mask alike, gets the transform of row b, in one launch:
+ *   out[i][j] = in[R(i - dy, h)][R(jj - dx, w)],  jj = flip ? w - 1 - j : j,
+ *   R(k, n) = k < 0 ? -k : (k >= n ? 2 (n - 1) - k : k)
+ * - a translation by (dy, dx) with reflected borders (the edge pixel is not repeated), then a left-right
+ * mirror: numpy.pad(a, S, mode='reflect')[..., S-dy : S-dy+h, S-dx : S-dx+w], mirrored when flip is set,
+ * for any S >= max(|dy|, |dx|).  Data movement only: every output word is a bit copy of an input word
+ * (NaN payloads and denormals included), every output word is written.
+ * max_shift bounds |dy| and |dx|: 0 <= max_shift <= min(h, w) - 1.  The kernel clamps the table's dy and dx
+ * to +-max_shift and uses flip & 1, so no table content can make it read outside a plane; a caller that
+ * wants its rows applied as they are keeps them in range (punet.kernels.augment checks host tables).
+ * t and t_out may be NULL with ct == 0.  1 <= batch <= 65535, cx >= 1, cx + ct <= 65535, h w <= 2^30;
+ * all pointers 4-byte aligned.  No output may overlap an input, the other output or the table.
+ * pu_flip_mean: out[b][i][j] = 0.5f * (y[b][i][j] + y_mirror[b][i][w - 1 - j]) in fp32 - one addition, then
+ * one multiplication - for maps [batch][h][w]: the mean of a prediction and the un-mirrored prediction of
+ * the mirrored image.  out == y is allowed; any other overlap of out with y, and any with y_mirror, is an
+ * error.  batch h < 2^31.
+ * Both: every check comes before the launch (PU_ERR_INVALID, messages starting with the entry's name);
+ * one launch, no workspace, no atomics, no host synchronisation: graph-capturable.
+ * ------------------------------------------------------------------------------------------- */
+int pu_augment(const float* x, const float* t, float* x_out, float* t_out, int batch, int cx, int ct, int h, int w,
+               const int* table, int max_shift, void* stream);
+int pu_flip_mean(const float* y, const float* y_mirror, float* out, int batch, int h, int w, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-tensor Adam (torch.optim.Adam, amsgrad=False, maximize=False):

@@ -5,7 +5,8 @@ BCE loss and fast_iou_metric on the host.  Here the samples go through the HIP f
 of ``batch`` slots (each slot with a zero trace - identical per-sample math), and the per-sample
 loss / metric averages are the reference's.  By default the loss and the pixel counts the metrics
 are made of come from one kernel call per chunk (kernels.seg_metrics) and one small table crosses
-to the host per pass; metrics="host" keeps the numpy path, which gives the same bits.
+to the host per pass; metrics="host" keeps the numpy path, which gives the same bits.  tta="hflip"
+(--tta hflip) scores the flip-averaged predictor of punet.augment.tta_forward instead, on either path.
 """
 from optparse import OptionParser
 
@@ -15,6 +16,7 @@ import torch
 from punet import bce_loss
 from punet import kernels as K
 from punet import metrics as pm
+from punet.augment import check_tta, tta_forward
 from utils import fast_iou_metric, iou_metric_batch, iou_score_from_counts
 
 
@@ -27,16 +29,16 @@ def _check_metrics(metrics):
         raise ValueError("metrics must be 'device' or 'host', not %r" % (metrics,))
 
 
-def _forward_chunk(net, X, y, s, e, device):
+def _forward_chunk(net, X, y, s, e, device, tta=None):
     """Zero-trace forward of samples [s, e): (probabilities [B, n], targets [B, n]) on the device."""
     xb = torch.from_numpy(np.asarray(X[s:e], dtype=np.float32)).to(device)
     tb = torch.from_numpy(np.asarray(y[s:e], dtype=np.float32)).to(device)
     B = xb.shape[0]
-    out, _ = net(xb, net.initialZeroHebb(B))          # zero trace per slot; the update is discarded
+    out = tta_forward(net, xb, tta)                   # zero trace per slot; the update is discarded
     return out.reshape(B, -1), tb.reshape(B, -1)
 
 
-def eval_net(net, X_val, y_val, device, criterion=None, debug=False, batch=32, metrics="device"):
+def eval_net(net, X_val, y_val, device, criterion=None, debug=False, batch=32, metrics="device", tta=None):
     """Returns (accuracy, loss) averaged over samples, as eval.py:66-103.
 
     metrics="device" (default, with criterion None): one kernels.seg_metrics call per chunk gives the
@@ -49,6 +51,7 @@ def eval_net(net, X_val, y_val, device, criterion=None, debug=False, batch=32, m
     numbers, the single process's.  metrics="host", or any criterion: the loss per slot and
     fast_iou_metric in numpy, every rank over the whole set."""
     _check_metrics(metrics)
+    check_tta(tta)
     net.eval()
     n = len(X_val)
     total_acc, total_loss = 0.0, 0.0
@@ -57,7 +60,7 @@ def eval_net(net, X_val, y_val, device, criterion=None, debug=False, batch=32, m
         table = pm.MetricTable(n, 0, device)
         with torch.no_grad():
             for s, e in pm.chunks_for_rank(n, batch, world, rank):
-                yf, tf = _forward_chunk(net, X_val, y_val, s, e, device)
+                yf, tf = _forward_chunk(net, X_val, y_val, s, e, device, tta)
                 table.add(s, *K.seg_metrics(yf, tf))
         table.finish()
         pixels = int(np.asarray(y_val[0]).size) if n else 1
@@ -68,7 +71,7 @@ def eval_net(net, X_val, y_val, device, criterion=None, debug=False, batch=32, m
         return total_acc / n, total_loss / n
     with torch.no_grad():
         for s in range(0, n, batch):
-            yf, tf = _forward_chunk(net, X_val, y_val, s, s + batch, device)
+            yf, tf = _forward_chunk(net, X_val, y_val, s, s + batch, device, tta)
             B = yf.shape[0]
             losses = torch.stack([criterion(yf[b], tf[b]) if criterion is not None else bce_loss(yf[b], tf[b])
                                   for b in range(B)])
@@ -81,7 +84,7 @@ def eval_net(net, X_val, y_val, device, criterion=None, debug=False, batch=32, m
     return total_acc / n, total_loss / n
 
 
-def iou_sweep(net, X, y, device, thresholds, batch=32, metrics="device"):
+def iou_sweep(net, X, y, device, thresholds, batch=32, metrics="device", tta=None):
     """The competition IoU score (iou_metric_batch) of the zero-trace predictions at every threshold:
     a float32 array, one score per threshold.
 
@@ -93,6 +96,7 @@ def iou_sweep(net, X, y, device, thresholds, batch=32, metrics="device"):
     back and iou_metric_batch runs per threshold in numpy.  The same bits either way.  Always the
     whole set on the calling process, whatever the process group."""
     _check_metrics(metrics)
+    check_tta(tta)
     net.eval()
     thresholds = [float(th) for th in thresholds]
     if metrics == "host":
@@ -100,7 +104,7 @@ def iou_sweep(net, X, y, device, thresholds, batch=32, metrics="device"):
         with torch.no_grad():
             for s in range(0, len(X), batch):
                 xb = torch.from_numpy(np.asarray(X[s:s + batch], dtype=np.float32)).to(device)
-                out, _ = net(xb, net.initialZeroHebb(xb.shape[0]))
+                out = tta_forward(net, xb, tta)
                 preds.append(out.cpu().numpy().reshape(xb.shape[0], 1, 1, out.shape[-2], out.shape[-1]))
         preds = np.concatenate(preds, 0)
         return np.array([iou_metric_batch(y, preds > np.float64(th)) for th in thresholds])
@@ -109,7 +113,7 @@ def iou_sweep(net, X, y, device, thresholds, batch=32, metrics="device"):
     tables = [pm.MetricTable(n, len(g), device) for g in groups]
     with torch.no_grad():
         for s, e in pm.chunks_for_rank(n, batch):
-            yf, tf = _forward_chunk(net, X, y, s, e, device)
+            yf, tf = _forward_chunk(net, X, y, s, e, device, tta)
             for g, table in zip(groups, tables):
                 table.add(s, *K.seg_metrics(yf, tf, g))
     scores = []
@@ -119,7 +123,7 @@ def iou_sweep(net, X, y, device, thresholds, batch=32, metrics="device"):
     return np.array(scores)
 
 
-def score_model_best_iou(net, X_valid, y_valid, device, debug=False, batch=32, metrics="device"):
+def score_model_best_iou(net, X_valid, y_valid, device, debug=False, batch=32, metrics="device", tta=None):
     """Threshold search by the best competition IoU (eval.py:20-64): zero-trace forward of every
     validation sample, 31 thresholds linspace(0.3, 0.7) mapped through the logit as the reference
     does, the score of iou_sweep per threshold; returns (threshold_best, iou_best).
@@ -129,7 +133,7 @@ def score_model_best_iou(net, X_valid, y_valid, device, debug=False, batch=32, m
     [N, 1, 1, H, W] - the comparison the reference intends - so the search completes."""
     thresholds_ori = np.linspace(0.3, 0.7, 31)
     thresholds = np.log(thresholds_ori / (1 - thresholds_ori))
-    ious = iou_sweep(net, X_valid, y_valid, device, thresholds, batch=batch, metrics=metrics)
+    ious = iou_sweep(net, X_valid, y_valid, device, thresholds, batch=batch, metrics=metrics, tta=tta)
     if debug:
         print(ious)
     k = int(np.argmax(ious))
@@ -144,6 +148,8 @@ def get_args():
     parser.add_option('-v', '--debug', action='store_true', dest='debug', default=False)
     parser.add_option('--model-type', dest='model_type', default='unetpres', help='unetpres | unetp')
     parser.add_option('--nbf', dest='nbf', type='int', default=101)
+    parser.add_option('--tta', dest='tta', default=None, type='choice', choices=['hflip'],
+                      help="test-time augmentation: hflip scores the mean of each prediction and its mirror's")
     (options, args) = parser.parse_args()
     return options
 
@@ -156,5 +162,5 @@ if __name__ == "__main__":
     net = cls(n_channels=1, n_classes=1, device=device, nbf=args.nbf)
     net.load_state_dict(torch.load(args.model, weights_only=True))
     d = np.load(args.data_dir)
-    acc, loss = eval_net(net, d["x_valid"], d["y_valid"], device)
+    acc, loss = eval_net(net, d["x_valid"], d["y_valid"], device, tta=args.tta)
     print("Validation accuracy: %f, loss: %f" % (acc, loss))

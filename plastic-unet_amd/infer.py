@@ -9,7 +9,9 @@ with the reference's columns (id, rle_mask).  The threshold and the encoding run
 host code on the probability maps.  start_inference() builds the reference's model
 (UNetpRes at the image width), loads the state dict with the weights-only loader, picks the mask
 threshold with eval.score_model_best_iou (whose reference version raises at S12 - see there) and
-predicts.
+predicts.  ``tta="hflip"`` (--tta hflip) on any of them: every prediction is the mean of the net's output
+on the image and its un-mirrored output on the mirrored image, merged on the device
+(punet.augment.tta_forward), so the threshold search, the threshold and the encoding see that predictor.
 """
 import csv
 import os
@@ -19,6 +21,7 @@ import numpy as np
 import torch
 
 from punet import kernels as K
+from punet.augment import check_tta, tta_forward
 from punet.rle import RunTable, compare_value
 from utils import encode
 
@@ -28,14 +31,15 @@ def inference(net, img_data, device):
     return predict_masks(net, np.asarray(img_data)[None], device)[0]
 
 
-def predict_masks(net, X, device, batch=32):
+def predict_masks(net, X, device, batch=32, tta=None):
     """Probability masks [N,H,W] of images X [N,C,H,W], zero trace per image."""
+    check_tta(tta)
     net.eval()
     out = []
     with torch.no_grad():
         for s in range(0, len(X), batch):
             xb = torch.from_numpy(np.asarray(X[s:s + batch], dtype=np.float32)).to(device)
-            y, _ = net(xb, net.initialZeroHebb(xb.shape[0]))
+            y = tta_forward(net, xb, tta)
             out.append(y.cpu().numpy())
     return np.concatenate(out, 0)
 
@@ -45,19 +49,20 @@ def _check_rle(rle):
         raise ValueError("rle must be 'device' or 'host', not %r" % (rle,))
 
 
-def predict_rle(net, X, device, thr, batch=32, keep=None):
+def predict_rle(net, X, device, thr, batch=32, keep=None, tta=None):
     """The strings encode(np.round(m > thr)) of the probability masks m of images X [N,C,H,W], with
     the threshold and the encoding on the device: per chunk only the run table comes back.  Chunk
     i + 1's forward and encode are enqueued before chunk i's table is read, so the device works while
     the host prints; the buffers of at most two chunks are alive.  ``keep``: a list that receives each
     chunk's probability maps on the host (for the PNG masks)."""
+    check_tta(tta)
     net.eval()
     th = compare_value(thr)
     out, waiting = [], None
     with torch.no_grad():
         for s in range(0, len(X), batch):
             xb = torch.from_numpy(np.asarray(X[s:s + batch], dtype=np.float32)).to(device)
-            y, _ = net(xb, net.initialZeroHebb(xb.shape[0]))
+            y = tta_forward(net, xb, tta)
             table = RunTable(*K.rle_encode(y.contiguous(), th))
             if waiting is not None:
                 out.extend(waiting.strings())
@@ -75,15 +80,17 @@ def _write_mask_png(path, mask):
     Image.fromarray(np.dstack((tmp, tmp, tmp))).save(path)
 
 
-def predict(net, test_df, params, visualize=False, save_masks=False, rle="device"):
+def predict(net, test_df, params, visualize=False, save_masks=False, rle="device", tta=None):
     """Threshold + RLE + CSV (infer.py:50-108).  test_df: the reference's test frame (index = image
     ids, column ``images``), or a pair (ids, X_test [N,C,H,W]).  params: out_dir, mask_threshold,
     img_chan/img_height/img_width (to shape the images), subm_file, device (default: the net's).
     ``visualize`` (matplotlib windows in the reference) is not supported on this host-less path.
     rle: "device" (default) thresholds and encodes on the device, and the probability maps come back
     only for ``save_masks``; "host" brings every map back and encodes it with utils.encode.  Both give
-    the same rows."""
+    the same rows.  tta: None or "hflip" (default: params.get("tta")), on either path."""
     _check_rle(rle)
+    tta = params.get("tta") if tta is None else tta
+    check_tta(tta)
     if isinstance(test_df, tuple):
         ids, X_test = test_df
         ids = list(ids)
@@ -96,10 +103,10 @@ def predict(net, test_df, params, visualize=False, save_masks=False, rle="device
     thr = params["mask_threshold"]
     if rle == "device":
         kept = [] if save_masks else None
-        codes = predict_rle(net, X_test, device, thr, keep=kept)
+        codes = predict_rle(net, X_test, device, thr, keep=kept, tta=tta)
         masks = np.concatenate(kept, 0) if kept else ()
     else:
-        masks = predict_masks(net, X_test, device)
+        masks = predict_masks(net, X_test, device, tta=tta)
     if save_masks:
         os.makedirs(os.path.join(params["out_dir"], "masks"), exist_ok=True)
         for fn, m in zip(ids, masks):
@@ -119,13 +126,15 @@ def predict(net, test_df, params, visualize=False, save_masks=False, rle="device
 
 def start_inference(model, test_df, X_valid, y_valid, out_dir, img_width, img_height, img_chan,
                     subm_file="submission.csv", gpu=True, visualize=False, save_masks=False, debug=False,
-                    mask_threshold=None, model_type="unetpres", rle="device"):
+                    mask_threshold=None, model_type="unetpres", rle="device", tta=None):
     """infer.py:110-179: the reference builds UNetpRes(n_channels=img_chan, n_classes=1,
     nbf=img_width), loads ``model`` (a state_dict path), scores the best threshold on the
     validation set and predicts.  ``mask_threshold`` skips the threshold search; ``model_type``
     'unetp' loads a UNetp instead.  The product path is the GPU one (``gpu`` is accepted for the
-    signature; there is no CPU fallback).  ``rle``: as in predict."""
+    signature; there is no CPU fallback).  ``rle``: as in predict.  ``tta`` goes to the threshold search and
+    to the prediction alike: the threshold is chosen for the predictor that is submitted."""
     _check_rle(rle)
+    check_tta(tta)
     from unet import UNetp, UNetpRes
     import eval as ev
     device = torch.device("cuda")
@@ -137,12 +146,12 @@ def start_inference(model, test_df, X_valid, y_valid, out_dir, img_width, img_he
     net.to(device)
     if mask_threshold is None:
         print("Score model for best IoU")
-        mask_threshold, iou_best = ev.score_model_best_iou(net, X_valid, y_valid, device, debug=debug)
+        mask_threshold, iou_best = ev.score_model_best_iou(net, X_valid, y_valid, device, debug=debug, tta=tta)
         print("Best threshold: %f, best IoU: %f" % (mask_threshold, iou_best))
     os.makedirs(out_dir, exist_ok=True)
     params = {"out_dir": out_dir, "device": device, "img_width": img_width, "img_height": img_height,
               "img_chan": img_chan, "mask_threshold": mask_threshold, "subm_file": subm_file, "debug": debug}
-    return predict(net, test_df, params, visualize=visualize, save_masks=save_masks, rle=rle)
+    return predict(net, test_df, params, visualize=visualize, save_masks=save_masks, rle=rle, tta=tta)
 
 
 def get_args():
@@ -161,6 +170,8 @@ def get_args():
     parser.add_option('--model-type', dest='model_type', default='unetpres', help='unetpres | unetp')
     parser.add_option('--rle', dest='rle', default='device', type='choice', choices=['device', 'host'],
                       help="where the masks are thresholded and run-length encoded: device | host")
+    parser.add_option('--tta', dest='tta', default=None, type='choice', choices=['hflip'],
+                      help="test-time augmentation: hflip averages each prediction with that of the mirrored image")
     (options, args) = parser.parse_args()
     return options
 
@@ -181,4 +192,4 @@ if __name__ == "__main__":
     start_inference(model=args.model, test_df=test_df, X_valid=x_valid, y_valid=y_valid, out_dir=args.out_dir,
                     gpu=args.gpu, img_width=w, img_height=h, img_chan=c, visualize=args.visualize,
                     save_masks=args.save, debug=True, mask_threshold=args.mask_threshold,
-                    model_type=args.model_type, rle=args.rle)
+                    model_type=args.model_type, rle=args.rle, tta=args.tta)

@@ -6,6 +6,7 @@ fp32, contiguous and resident on the ROCm device; activations are NHWC.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -17,7 +18,7 @@ from ._lib import (ConvArgs, WgradArgs, PlasticArgs, PlasticHeadArgs, PlasticBwd
 
 __all__ = ["KernelProfiler", "igemm", "wgrad", "pack_weight", "nchw_to_nhwc", "maxpool2_fwd", "maxpool2_bwd",
            "outconv_fwd", "outconv_bwd", "plastic_fwd", "trace_update", "plastic_bwd", "plastic_bwd_trace", "bce_fwd",
-           "bce_bwd", "seg_metrics", "rle_encode", "lovasz_fwd", "lovasz_bwd", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
+           "bce_bwd", "seg_metrics", "rle_encode", "augment", "flip_mean", "lovasz_fwd", "lovasz_bwd", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
 
 
 def lib():
@@ -751,6 +752,80 @@ def rle_encode(y, threshold, cap=None):
         check(L.pu_rle_encode(y.data_ptr(), B, H, W, float(threshold), offsets.data_ptr(), runs.data_ptr() or None, cap,
                               ws.data_ptr(), nbytes, _stream()), "pu_rle_encode")
     return offsets, runs
+
+
+def check_augment_table(table, batch, max_shift):
+    """A host table of augment rows -> int32 numpy [batch, 4], or ValueError: rows {flip, dy, dx, 0} with
+    flip in {0, 1} and |dy|, |dx| <= max_shift (the kernel would clamp them; a host table says what it
+    means)."""
+    rows = table.numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    if rows.shape != (batch, 4):
+        raise ValueError("augment: the table must be [%d, 4] {flip, dy, dx, 0} rows (got shape %s)" % (batch, rows.shape))
+    if rows.dtype.kind not in "iu":
+        raise ValueError("augment: the table must hold integers (got %s)" % rows.dtype)
+    if rows.size and not np.isin(rows[:, 0], (0, 1)).all():
+        raise ValueError("augment: a flip outside {0, 1}")
+    if rows.size and (np.abs(rows[:, 1:3].astype(np.int64)) > max_shift).any():
+        raise ValueError("augment: a shift outside +-%d (max_shift)" % max_shift)
+    return np.ascontiguousarray(rows, dtype=np.int32)
+
+
+def augment(x, t, table, max_shift, out=None):
+    """Flip and reflected shift of a batch (pu_augment): x [B, Cx, H, W] and t [B, Ct, H, W] or None ->
+    (x_out, t_out) (t_out None with t); slot b's planes, image and mask alike, transformed by table row
+    b = {flip, dy, dx, 0} - see plastic_unet.h.  table: a device int32 tensor [B, 4], used as it is (the
+    kernel clamps its shifts to +-max_shift), or a host array / CPU tensor, checked here (ValueError) and
+    uploaded.  out: None (new tensors) or the pair (x_out, t_out) to write, neither overlapping an input."""
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError("augment: x must be [B, C, H, W] with no empty axis (got shape %s)" % (tuple(x.shape),))
+    B, cx, H, W = x.shape
+    ct = 0
+    if t is not None:
+        if t.dim() != 4 or t.shape[0] != B or tuple(t.shape[2:]) != (H, W) or t.numel() == 0:
+            raise ValueError("augment: t must be [%d, C, %d, %d] like x (got shape %s)" % (B, H, W, tuple(t.shape)))
+        ct = t.shape[1]
+    max_shift = int(max_shift)
+    if not 0 <= max_shift <= min(H, W) - 1:
+        raise ValueError("augment: max_shift %d outside 0 .. min(H, W) - 1 = %d" % (max_shift, min(H, W) - 1))
+    on_device = isinstance(table, torch.Tensor) and table.is_cuda
+    if on_device:
+        _req(table, "table", torch.int32)
+        if tuple(table.shape) != (B, 4):
+            raise ValueError("augment: the table must be [%d, 4] (got shape %s)" % (B, tuple(table.shape)))
+    else:
+        rows = check_augment_table(table, B, max_shift)      # before the images are looked at: a host-only check
+    _req(x, "x"); _req(t, "t")
+    if not on_device:
+        table = torch.from_numpy(rows).to(x.device)
+    if out is None:
+        x_out = torch.empty_like(x)
+        t_out = torch.empty_like(t) if t is not None else None
+    else:
+        x_out, t_out = out
+        _req(x_out, "x_out"); _req(t_out, "t_out")
+        if x_out.shape != x.shape or (t is None) != (t_out is None) or (t is not None and t_out.shape != t.shape):
+            raise ValueError("augment: out must be (x_out, t_out) shaped like (x, t)")
+    with _Rec("augment", nbytes=8.0 * (x.numel() + (t.numel() if t is not None else 0))):
+        check(lib().pu_augment(x.data_ptr(), _p(t), x_out.data_ptr(), _p(t_out), B, cx, ct, H, W, table.data_ptr(),
+                               max_shift, _stream()), "pu_augment")
+    return x_out, t_out
+
+
+def flip_mean(y, y_mirror, out=None):
+    """out = 0.5 * (y + y_mirror mirrored left-right) (pu_flip_mean): y and y_mirror [..., H, W] of one
+    shape, the prediction of a batch and of its mirrored images.  out: None (a new tensor) or y itself."""
+    _req(y, "y"); _req(y_mirror, "y_mirror"); _req(out, "out")
+    if y.dim() < 2 or y.numel() == 0:
+        raise ValueError("flip_mean: y must be [..., H, W] with no empty axis (got shape %s)" % (tuple(y.shape),))
+    if y_mirror.shape != y.shape or (out is not None and out.shape != y.shape):
+        raise ValueError("flip_mean: y %s, y_mirror %s and out must have one shape" % (tuple(y.shape), tuple(y_mirror.shape)))
+    if out is None:
+        out = torch.empty_like(y)
+    H, W = y.shape[-2:]
+    with _Rec("flip_mean", nbytes=12.0 * y.numel()):
+        check(lib().pu_flip_mean(y.data_ptr(), y_mirror.data_ptr(), out.data_ptr(), y.numel() // (H * W), H, W, _stream()),
+              "pu_flip_mean")
+    return out
 
 
 LOVASZ_MAX_N = 16384    # pixels per image one workgroup sorts in LDS (csrc/lovasz.hip)

@@ -13,9 +13,20 @@ compute stream has recorded that it finished the step reading it; a pinned slot 
 after the copy that read it has completed (host waits on that event).  On a CPU device the same
 iterator degenerates to plain copies (test harness for the ordering logic; the product trains on
 the GPU).
+
+With an augmentation plan (punet/augment.py) slot k also carries the batch's rows of the epoch's table
+(pinned, and a device copy) and a second pair of device buffers:
+
+  pinned slot k  --async H2D-->  raw device slot k  --kernels.augment on the copy stream-->  augmented slot k
+
+and it is the augmented pair that the compute stream reads, so the wait on ``consumed[k]`` comes before
+that launch; the raw pair is touched by the copy stream alone.  The kernel runs under the previous step
+like the copies do.
 """
 import numpy as np
 import torch
+
+from . import kernels as K
 
 
 class BatchPrefetcher:
@@ -23,9 +34,12 @@ class BatchPrefetcher:
 
     X: [N, ...] inputs, Y: [N, ...] targets (numpy or torch CPU).  Yielded tensors are float32
     views of the device slot; they stay valid until the iterator advances ``depth - 1`` more
-    times (the trainer consumes them within its step)."""
+    times (the trainer consumes them within its step).
 
-    def __init__(self, X, Y, ranges, device, depth=2):
+    augment: None, or an AugmentPlan over the samples of X: sample i of epoch e (set_epoch) is yielded
+    transformed by row i of plan.table(e), image and mask alike, whatever batch it is in."""
+
+    def __init__(self, X, Y, ranges, device, depth=2, augment=None):
         self.X, self.Y = X, Y
         self.ranges = list(ranges)
         self.device = torch.device(device)
@@ -45,9 +59,35 @@ class BatchPrefetcher:
             self.copied = [torch.cuda.Event() for _ in range(self.depth)]
             self.consumed = [None] * self.depth
             self.pinned_busy = [None] * self.depth
+        self.plan = augment if augment is not None and augment.spec else None
+        if self.plan is not None and bmax:
+            if len(xs) != 3 or len(ys) not in (2, 3) or tuple(ys[-2:]) != tuple(xs[-2:]):
+                raise ValueError("augment: X must be [N, C, H, W] and Y [N, C, H, W] or [N, H, W] of the same H x W "
+                                 "(got %s and %s)" % ((len(X),) + xs, (len(Y),) + ys))
+            if self.plan.n_samples < max(hi for _, hi in self.ranges):
+                raise ValueError("augment: a plan for %d samples, batches up to sample %d" % (
+                    self.plan.n_samples, max(hi for _, hi in self.ranges)))
+            self.plan.spec.check_fits(*xs[-2:])
+            self.rows_host = [torch.empty((bmax, 4), dtype=torch.int32, pin_memory=self.gpu) for _ in range(self.depth)]
+            self.rows_dev = [torch.empty((bmax, 4), dtype=torch.int32, device=self.device) for _ in range(self.depth)]
+            self.aug = [(torch.empty_like(dx), torch.empty_like(dy)) for dx, dy in self.dev]
+            self.set_epoch(0)
 
     def __len__(self):
         return len(self.ranges)
+
+    def set_epoch(self, epoch):
+        """The epoch whose table the next iteration applies (nothing to do without a plan)."""
+        self.epoch = int(epoch)
+        if self.plan is not None:
+            self.table = self.plan.table(self.epoch)
+
+    def _augment(self, k, lo, n):
+        """raw slot k -> augmented slot k by the rows of the samples lo .. lo + n, on the current stream"""
+        (dx, dy), (ax, ay) = self.dev[k], self.aug[k]
+        rows = self.rows_dev[k][:n] if self.gpu else self.table[lo:lo + n]
+        planes = (lambda v: v[:n].unsqueeze(1)) if dy.dim() == 3 else (lambda v: v[:n])
+        K.augment(dx[:n], planes(dy), rows, self.plan.max_shift, out=(ax[:n], planes(ay)))
 
     def _fill(self, i):
         """stage batch i into its pinned slot and issue its H2D copy"""
@@ -60,15 +100,22 @@ class BatchPrefetcher:
             self.pinned_busy[k].synchronize()      # the copy that last read this pinned slot is done
         np.copyto(hx[:n].numpy(), np.asarray(self.X[lo:hi]), casting="same_kind")
         np.copyto(hy[:n].numpy(), np.asarray(self.Y[lo:hi]), casting="same_kind")
+        if self.plan is not None:
+            np.copyto(self.rows_host[k][:n].numpy(), self.table[lo:hi])
         if not self.gpu:
             dx[:n].copy_(hx[:n])
             dy[:n].copy_(hy[:n])
+            if self.plan is not None:
+                self._augment(k, lo, n)
             return
         with torch.cuda.stream(self.stream):
             if self.consumed[k] is not None:
                 self.stream.wait_event(self.consumed[k])   # compute finished the step that read slot k
             dx[:n].copy_(hx[:n], non_blocking=True)
             dy[:n].copy_(hy[:n], non_blocking=True)
+            if self.plan is not None:
+                self.rows_dev[k][:n].copy_(self.rows_host[k][:n], non_blocking=True)
+                self._augment(k, lo, n)             # after the wait on consumed[k]: compute reads the augmented pair
             self.copied[k].record(self.stream)
         self.pinned_busy[k] = self.copied[k]
 
@@ -92,7 +139,7 @@ class BatchPrefetcher:
             n = hi - lo
             if self.gpu:
                 torch.cuda.current_stream(self.device).wait_event(self.copied[k])
-            dx, dy = self.dev[k]
+            dx, dy = self.dev[k] if self.plan is None else self.aug[k]
             yield dx[:n], dy[:n]
             if self.gpu:
                 ev = torch.cuda.Event()

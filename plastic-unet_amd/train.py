@@ -15,6 +15,10 @@ save checkpoints (:153-203).  Differences, all opt-in:
                    Adam step; the per-step norms are logged as train/grad_norms (0: off)
   --loss NAME      bce (default, the reference) | lovasz | bce+lovasz (bce + --lovasz-weight * lovasz): the
                    training loss, which is also the one logged; validation stays BCE and accuracy
+  --augment SPEC   hflip, shift:S or both (comma-separated): every epoch each training sample is shifted by a
+                   random (dy, dx) within +-S with reflected borders and mirrored left-right at random, image
+                   and mask alike, on the device (punet/augment.py; rows seeded by --augment-seed, default
+                   --seed); validation data is never augmented
   --resident       keep the whole training set in HBM; default: batches stream host -> HBM through
                    pinned, double-buffered asynchronous copies (punet/loader.py) under the previous step
 Data-parallel training: launch with torch.distributed.run; each rank trains its contiguous shard
@@ -40,6 +44,8 @@ if HERE not in sys.path:
 
 from unet import UNetp, UNetpRes  # noqa: E402
 from punet import dp  # noqa: E402
+from punet import kernels as K  # noqa: E402
+from punet.augment import AugmentPlan, parse_augment  # noqa: E402
 from punet.engine import Trainer  # noqa: E402
 from punet.loader import BatchPrefetcher  # noqa: E402
 from eval import eval_net  # noqa: E402
@@ -79,14 +85,24 @@ def train(net, X_train, X_val, y_train, y_val, params):
                       max_grad_norm=clip_grad if clip_grad > 0 else None, loss=params.get("loss", "bce"),
                       lovasz_weight=float(params.get("lovasz_weight", 1.0)))
     ranges = list(_batches(samples_count, bs, world, rank))
-    if params.get("prefetch", True):
+    # the training batches alone are augmented: a row per sample and epoch, the same on every rank and path
+    spec = parse_augment(params.get("augment"), hw=tuple(np.shape(X_train)[-2:]))
+    plan = None
+    if spec:
+        seed = params.get("augment_seed")
+        plan = AugmentPlan(spec, samples_count, int(seed) if seed is not None else 0)
+    prefetch = params.get("prefetch", True)
+    if prefetch:
         # stream batches host -> HBM (pinned, double-buffered, overlapping the previous step)
-        batches = BatchPrefetcher(X_train, y_train, ranges, device)
+        batches = BatchPrefetcher(X_train, y_train, ranges, device, augment=plan)
     else:
         # the whole training set resident in HBM (copied once)
         X_dev = torch.from_numpy(np.asarray(X_train, dtype=np.float32)).to(device)
         Y_dev = torch.from_numpy(np.asarray(y_train, dtype=np.float32)).to(device)
-        batches = [(X_dev[lo:hi], Y_dev[lo:hi]) for lo, hi in ranges]
+        if plan is None:
+            batches = [(X_dev[lo:hi], Y_dev[lo:hi]) for lo, hi in ranges]
+        elif Y_dev.dim() == 3:
+            Y_dev = Y_dev.unsqueeze(1)              # [N, H, W] masks as one plane per sample (batches: per epoch)
     if params["stop_time"] > 0 and verbose:
         print("Training started at: [%s] and set to stop at: [%s]" % (
             datetime.fromtimestamp(time.time()).strftime("%B %d, %Y %H:%M:%S"),
@@ -94,6 +110,12 @@ def train(net, X_train, X_val, y_train, y_val, params):
     for epoch in range(params["epochs"]):
         net.train()
         epoch_start_time = time.time()
+        if prefetch:
+            batches.set_epoch(epoch)
+        elif plan is not None:
+            # the epoch's rows go up once; each batch slice is augmented as the loop reaches it
+            rows = torch.from_numpy(plan.table(epoch)).to(device)
+            batches = (K.augment(X_dev[lo:hi], Y_dev[lo:hi], rows[lo:hi], plan.max_shift) for lo, hi in ranges)
         seq = getattr(net, "hebb_mode", "slots") == "sequential"
         # trace reset per epoch (train.py:88): per-slot traces, or one trace threaded through
         hebb = net.initialZeroHebb() if seq else net.initialZeroHebb(bs)
@@ -192,7 +214,7 @@ def start_train(x_train, x_valid, y_train, y_valid, out_dir, model, img_width, i
                 save_every=100, gamma=0.666, steplr=1e6, rollout=50000, prule="hebb", debug=False,
                 model_type="unetpres", depth=5, base_ch=8, neurons=16, batch_size=1, hebb_mode="slots",
                 batch_norm=False, bilinear_upsample=False, prefetch=True, bptt=0, clip_grad=0.0, loss="bce",
-                lovasz_weight=1.0):
+                lovasz_weight=1.0, augment="", augment_seed=None):
     world, rank, local = dp.init_from_env()
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
@@ -201,7 +223,8 @@ def start_train(x_train, x_valid, y_train, y_valid, out_dir, model, img_width, i
               "val_ratio": val_ratio, "val_every": val_every, "save_every": save_every, "rollout": rollout,
               "gamma": gamma, "steplr": steplr, "prule": prule, "im_width": img_width, "im_height": img_height,
               "im_chan": img_chan, "debug": debug, "batch_size": batch_size, "prefetch": prefetch,
-              "bptt": bptt, "clip_grad": clip_grad, "loss": loss, "lovasz_weight": lovasz_weight}
+              "bptt": bptt, "clip_grad": clip_grad, "loss": loss, "lovasz_weight": lovasz_weight,
+              "augment": augment, "augment_seed": augment_seed}
     if model_type == "unetp":
         net = UNetp(n_channels=img_chan, n_classes=1, nbf=img_width, batch_norm=batch_norm,
                     bilinear_upsample=bilinear_upsample, device=device, rule=prule, depth=depth, base_ch=base_ch,
@@ -266,6 +289,11 @@ def parse_args(argv=None):
                            'on probabilities, per image, up to 128 x 128) or bce+lovasz; validation stays BCE')
     parser.add_option('--lovasz-weight', dest='lovasz_weight', type='float', default=1.0,
                       help='w of --loss bce+lovasz: bce + w * lovasz')
+    parser.add_option('--augment', dest='augment', default='',
+                      help="training augmentation on the device, comma-separated: hflip (random left-right mirror), "
+                           "shift:S (random translation by up to S pixels each way, reflected borders); '': off")
+    parser.add_option('--augment-seed', dest='augment_seed', type='int', default=None,
+                      help='seed of the augmentation rows (default: --seed)')
     parser.add_option('--seed', dest='seed', type='int', default=0)
     parser.add_option('--resident', dest='resident', action='store_true', default=False,
                       help='copy the whole training set to HBM once instead of streaming batches')
@@ -304,4 +332,5 @@ if __name__ == '__main__':
                 debug=args.debug, model_type=args.model_type, depth=args.depth, base_ch=args.base_ch,
                 neurons=args.neurons, batch_size=args.batch_size, hebb_mode=args.hebb_mode,
                 batch_norm=args.batch_norm, bilinear_upsample=args.bilinear, prefetch=not args.resident,
-                bptt=args.bptt, clip_grad=args.clip_grad, loss=args.loss, lovasz_weight=args.lovasz_weight)
+                bptt=args.bptt, clip_grad=args.clip_grad, loss=args.loss, lovasz_weight=args.lovasz_weight,
+                augment=args.augment, augment_seed=args.seed if args.augment_seed is None else args.augment_seed)

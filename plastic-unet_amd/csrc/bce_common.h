@@ -1,7 +1,7 @@
 // What plastic.hip (bce_partial_kernel, bce_final_kernel) and metrics.hip (seg_metrics_partial_kernel,
 // seg_metrics_finish_kernel) share: the element expression of nn.BCELoss, the grid of a sum over n
-// elements, the 256-wide fp64 tree and the finish.  One copy of each, so the mean BCE of a sample has
-// the same bits whichever entry point computes it.
+// elements and the finish (over common.h's block_tree256).  One copy of each, so the mean BCE of a
+// sample has the same bits whichever entry point computes it.
 #pragma once
 
 #include "common.h"
@@ -26,24 +26,11 @@ __device__ __forceinline__ float bce_element(float yy, float tt) {
     return (tt - 1.f) * fmaxf(log1pf(-yy), -100.f) - tt * fmaxf(logf(yy), -100.f);
 }
 
-// sum over the block's 256 threads by a halving tree through LDS, valid in thread 0; every thread of
-// the block calls it
-__device__ __forceinline__ double bce_block_tree(double s) {
-    __shared__ double red[256];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // the np block partials -> the mean over n, valid in thread 0 of the one block that calls it
 __device__ __forceinline__ float bce_finish(const double* __restrict__ partial, int np, long long n) {
     double s = 0.0;
     for (int i = threadIdx.x; i < np; i += blockDim.x) s += partial[i];
-    return (float)(bce_block_tree(s) / (double)n);
+    return (float)(block_tree256(s) / (double)n);
 }
 
 }  // namespace pu

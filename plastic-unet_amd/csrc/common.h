@@ -126,6 +126,32 @@ __device__ __forceinline__ float dot4_fma(const V v, const V w) {
     return fmaf(v[3], w[3], fmaf(v[2], w[2], fmaf(v[1], w[1], v[0] * w[0])));
 }
 
+// sum over the L lanes (a power of two up to 16) that share a pixel, by an xor tree inside the
+// 16-lane group: the other half of that promise.  outconv_fwd_kernel always runs L = 16 (idle lanes
+// carry zeros); the fused head runs L = C / 4 lanes and skips the steps that would add those zeros.
+template <int L>
+__device__ __forceinline__ float lane_tree16(float t) {
+    if (L >= 16) t += __shfl_xor(t, 8, 16);
+    if (L >= 8) t += __shfl_xor(t, 4, 16);
+    if (L >= 4) t += __shfl_xor(t, 2, 16);
+    if (L >= 2) t += __shfl_xor(t, 1, 16);
+    return t;
+}
+
+// fp64 sum over the block's 256 threads by a halving tree through LDS, valid in thread 0; every
+// thread of the block calls it.  The first barrier comes after the write of `s`, so it also
+// publishes whatever else the caller stored to LDS before the call.
+__device__ __forceinline__ double block_tree256(double s) {
+    __shared__ double red[256];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 // XCD-aware block order: the dispatcher deals blocks round-robin over the 8 XCDs (block b runs on
 // XCD b % 8).  Map hardware block b to a logical tile so that each XCD gets one CONTIGUOUS range
 // of logical tiles (neighbouring tiles share input rows/halos -> reuse in that XCD's L2).

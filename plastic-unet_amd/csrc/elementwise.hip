@@ -407,10 +407,7 @@ __global__ void outconv_fwd_kernel(const T* __restrict__ x, const float* __restr
             f32x4 ww = *reinterpret_cast<const f32x4*>(w + c);
             s += dot4_fma(v, ww);
         }
-        s += __shfl_xor(s, 8, 16);
-        s += __shfl_xor(s, 4, 16);
-        s += __shfl_xor(s, 2, 16);
-        s += __shfl_xor(s, 1, 16);
+        s = lane_tree16<16>(s);
         if (lane16 == 0) y[m] = s + bias;
     }
 }
@@ -538,19 +535,13 @@ __global__ __launch_bounds__(256) void outconv_bwd_narrow_kernel(const T* __rest
 // one block per column: fixed-order fp64 tree over the per-block partials
 __global__ void column_sum_kernel(const float* __restrict__ partial, int nparts, int cols, float* __restrict__ dw,
                                   float* __restrict__ db) {
-    __shared__ double red[256];
     const int c = blockIdx.x;
     double s = 0.0;
     for (int q = threadIdx.x; q < nparts; q += 256) s += partial[(long long)q * (cols + 1) + c];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    s = block_tree256(s);
     if (threadIdx.x == 0) {
-        if (c < cols) dw[c] = (float)red[0];
-        else db[0] = (float)red[0];
+        if (c < cols) dw[c] = (float)s;
+        else db[0] = (float)s;
     }
 }
 
@@ -702,17 +693,11 @@ __global__ void colsum_partial_kernel(const float* __restrict__ x, long long row
 // sums in a fixed thread order, then a fixed LDS tree (deterministic)
 __global__ void colsum_final_kernel(const double* __restrict__ part, int nparts, int cols, float* __restrict__ out,
                                     int accumulate) {
-    __shared__ double red[256];
     const int c = blockIdx.x;
     double s = 0.0;
     for (int q = threadIdx.x; q < nparts; q += 256) s += part[(long long)q * cols + c];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[c] = accumulate ? out[c] + (float)red[0] : (float)red[0];
+    s = block_tree256(s);
+    if (threadIdx.x == 0) out[c] = accumulate ? out[c] + (float)s : (float)s;
 }
 
 static int colsum_blocks(long long rows) {

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void seg_metrics_partial_kernel(const float* _
             }
         }
     }
-    s = bce_block_tree(s);                                // its barriers also order wave_count
+    s = block_tree256(s);                                // its barriers also order wave_count
     const long long block = (long long)blockIdx.y * gridDim.x + blockIdx.x;
     if (threadIdx.x == 0) loss_partial[block] = s;
     if ((int)threadIdx.x < cols)

@@ -464,7 +464,7 @@ def _zero(t):
 
 
 def trace_np(H, x0, y0, eta, rule, mutant=None):
-    """H' in numpy float32, one operation at a time, in the order of trace_rule (csrc/plastic.hip):
+    """H' in numpy float32, one operation at a time, in the order of trace_rule (csrc/head_common.h):
     H [B, N, N], x0 / y0 [B, N], eta a float32"""
     f = np.float32
     H, x0, y0, eta = (np.asarray(t, dtype=f) for t in (H, x0, y0, eta))

@@ -32,6 +32,8 @@
  *                      call site: an extension, the surrogate of the IoU that validation reports)
  *   pu_augment         random flips and reflected shifts of a training batch, images and masks alike (no
  *   pu_flip_mean       reference call site: extensions) - and the mean of a prediction with its mirror's
+ *   pu_fit             data of one size to a net of another: reflect-pad, crop, bilinear resize (no reference
+ *                      call site: an extension; the resize is skimage's of src/utils/img_utils.py:16-24)
  *   pu_adam_multi     torch.optim.Adam.step           src/train.py:66,111
  *   pu_grad_norm       torch.nn.utils.clip_grad_norm_ (no reference call site: an extension for
  *   pu_adam_multi_clipped  episode training) - the norm and coefficient, and Adam on the scaled g
@@ -585,6 +587,34 @@ int pu_lovasz_bwd(const float* dtab, const float* grad_loss, int batch, int n, f
 int pu_augment(const float* x, const float* t, float* x_out, float* t_out, int batch, int cx, int ct, int h, int w,
                const int* table, int max_shift, void* stream);
 int pu_flip_mean(const float* y, const float* y_mirror, float* out, int batch, int h, int w, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Fitting data of one size to a net of another (no reference call site: an extension).
+ * pu_fit gathers `planes` planes in [h][w] (fp32, contiguous) into planes out [H][W], all by one map:
+ *   PU_FIT_PAD     H >= h, W >= w:  out[i][j] = in[R(i - top, h)][R(j - left, w)], the reflection R of
+ *                  pu_augment (the edge pixel is not repeated): numpy.pad(in, ((top, H - h - top),
+ *                  (left, W - w - left)), mode='reflect').  0 <= top <= h - 1 and H - h - top <= h - 1,
+ *                  0 <= left <= w - 1 and W - w - left <= w - 1: no reflection leaves the plane.
+ *   PU_FIT_CROP    H <= h, W <= w:  out[i][j] = in[top + i][left + j];  0 <= top <= h - H, 0 <= left <= w - W.
+ *   PU_FIT_RESIZE  any H, W; top = left = 0.  Bilinear with the sample points at the pixel centres and
+ *                  zeros outside the plane: skimage.transform.resize(order=1, mode='constant', cval=0)
+ *                  without anti-aliasing, as utils/data_set.py restates it.  The source coordinate of
+ *                  output row r is the exact rational ((2 r + 1) h - H) / (2 H), taken apart in integers:
+ *                    n = (2 r + 1) h - H,  y0 = floor(n / 2H),  fy = (float)((n mod 2H) / 2H)
+ *                  (mathematical floor and mod; the quotient rounded to fp32 once), gy = 1.0f - fy; columns
+ *                  likewise give x0, fx, gx.  With a = in[y0][x0], b = in[y0][x0 + 1], c = in[y0 + 1][x0],
+ *                  d = in[y0 + 1][x0 + 1], each 0 where its row or column lies outside the plane:
+ *                    top = fmaf(b, fx, a * gx);  bot = fmaf(d, fx, c * gx);  out = fmaf(bot, fy, top * gy)
+ *                  in fp32, in this order, never contracted otherwise: the same bits on every call.
+ * PAD and CROP move data only: every output word is a bit copy of an input word (NaN payloads and
+ * denormals included).  Every output word is written, by one lane.  CROP with the offsets of a PAD undoes it.
+ * planes >= 1, h w <= 2^30 and H W <= 2^30; in and out 4-byte aligned and not overlapping.  Every check
+ * comes before the launch (PU_ERR_INVALID, messages starting with "pu_fit:"); one launch, no workspace,
+ * no atomics, no host synchronisation: graph-capturable.
+ * ------------------------------------------------------------------------------------------- */
+enum { PU_FIT_PAD = 0, PU_FIT_CROP = 1, PU_FIT_RESIZE = 2 };
+int pu_fit(const float* in, float* out, long long planes, int h, int w, int H, int W, int mode, int top, int left,
+           void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-tensor Adam (torch.optim.Adam, amsgrad=False, maximize=False):

@@ -146,6 +146,7 @@ SIGNATURES = [
     ("pu_lovasz_bwd", c_int, [P, P, c_int, c_int, P, P]),
     ("pu_augment", c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P]),
     ("pu_flip_mean", c_int, [P, P, P, c_int, c_int, c_int, P]),
+    ("pu_fit", c_int, [P, P, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     ("pu_bn_workspace_bytes", c_size, [c_int, c_ll, c_int]),
     ("pu_bn_fwd", c_int, [P, P, P, P, P, P, P, P, c_int, c_ll, c_int, c_float, c_float, c_int, c_int, P, P, c_size, P]),
     ("pu_bn_bwd", c_int, [P, P, P, P, P, P, P, P, c_int, c_ll, c_int, P, P, P, c_size, P]),

@@ -8,7 +8,8 @@ host, one table per epoch (AugmentPlan), and applied on the device: by the prefe
 
 Inference (``--tta hflip``): the prediction of a batch is the mean of the net's output on the images and
 its un-mirrored output on the mirrored images (tta_forward), merged on the device so that the threshold,
-the metrics and the run-length encoding that follow stay there.
+the metrics and the run-length encoding that follow stay there.  With a FitSpec (punet/fit.py: the net's side is
+not the data's) each of the two forwards is fitted to the net and brought back, and the merge is at the data size.
 """
 import numpy as np
 import torch
@@ -126,16 +127,23 @@ def check_tta(tta):
         raise ValueError("tta must be None or 'hflip', not %r" % (tta,))
 
 
-def tta_forward(net, xb, tta=None):
+def tta_forward(net, xb, tta=None, fit=None):
     """The zero-trace forward every prediction path goes through: xb [B, C, H, W] -> probabilities.
     tta None: net(xb, zero trace) as it is.  'hflip': two forwards of the same batch size, each with a
     fresh zero trace - xb, then xb mirrored left-right (kernels.augment with mirror_table) - merged by
-    kernels.flip_mean: 0.5 * (y + mirror(y_mirror)), on the device."""
+    kernels.flip_mean: 0.5 * (y + mirror(y_mirror)), on the device.
+    fit: None, or the punet.fit.FitSpec of a net whose side is not the data's: a forward is then
+    P(x) = fit.to_data(net(fit.to_net(x), zero trace)), so xb and the result are at the data size, and so are
+    the mirror and the merge of 'hflip'."""
     check_tta(tta)
     B = xb.shape[0]
-    y, _ = net(xb, net.initialZeroHebb(B))
+
+    def forward(x):
+        y, _ = net(fit.to_net(x.contiguous()) if fit else x, net.initialZeroHebb(B))
+        return fit.to_data(y.contiguous()) if fit else y
+
+    y = forward(xb)
     if tta is None:
         return y
     xm, _ = K.augment(xb.contiguous(), None, _mirror_rows(B, xb.device), 0)
-    ym, _ = net(xm, net.initialZeroHebb(B))
-    return K.flip_mean(y.contiguous(), ym.contiguous())
+    return K.flip_mean(y.contiguous(), forward(xm).contiguous())

@@ -18,7 +18,7 @@ from ._lib import (ConvArgs, WgradArgs, PlasticArgs, PlasticHeadArgs, PlasticBwd
 
 __all__ = ["KernelProfiler", "igemm", "wgrad", "pack_weight", "nchw_to_nhwc", "maxpool2_fwd", "maxpool2_bwd",
            "outconv_fwd", "outconv_bwd", "plastic_fwd", "trace_update", "plastic_bwd", "plastic_bwd_trace", "bce_fwd",
-           "bce_bwd", "seg_metrics", "rle_encode", "augment", "flip_mean", "lovasz_fwd", "lovasz_bwd", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
+           "bce_bwd", "seg_metrics", "rle_encode", "augment", "flip_mean", "fit", "lovasz_fwd", "lovasz_bwd", "adam_multi", "grad_norm", "pack_weights", "round16", "cgroup_for", "device_info", "lib"]
 
 
 def lib():
@@ -825,6 +825,51 @@ def flip_mean(y, y_mirror, out=None):
     with _Rec("flip_mean", nbytes=12.0 * y.numel()):
         check(lib().pu_flip_mean(y.data_ptr(), y_mirror.data_ptr(), out.data_ptr(), y.numel() // (H * W), H, W, _stream()),
               "pu_flip_mean")
+    return out
+
+
+FIT_MODES = {"pad": 0, "crop": 1, "resize": 2}     # PU_FIT_PAD, PU_FIT_CROP, PU_FIT_RESIZE
+
+
+def fit(x, size, mode, top=0, left=0, out=None):
+    """Planes of one size gathered into planes of another (pu_fit): x [..., h, w] -> [..., H, W], size = (H, W)
+    or one side S.  mode 'pad': reflected borders (the edge pixel not repeated), `top` rows above and `left`
+    columns before the data - numpy.pad(mode='reflect'); 'crop': the H x W window at (top, left); both are bit
+    copies.  'resize': bilinear with zeros outside, skimage's resize(order=1, mode='constant') as
+    utils.data_set.resize_bilinear_constant restates it - see plastic_unet.h for the order of its arithmetic.
+    out: None (a new tensor) or the tensor to write, not overlapping x."""
+    if mode not in FIT_MODES:
+        raise ValueError("fit: mode must be 'pad', 'crop' or 'resize', not %r" % (mode,))
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError("fit: x must be [..., h, w] with no empty axis (got shape %s)" % (tuple(x.shape),))
+    H, W = (int(size), int(size)) if np.ndim(size) == 0 else (int(size[0]), int(size[1]))
+    h, w = x.shape[-2:]
+    top, left = int(top), int(left)
+    if H < 1 or W < 1 or h * w > 1 << 30 or H * W > 1 << 30:
+        raise ValueError("fit: planes of %d x %d to %d x %d (1 .. 2^30 pixels each)" % (h, w, H, W))
+    if mode == "pad":
+        if H < h or W < w:
+            raise ValueError("fit: pad of %d x %d to a smaller %d x %d" % (h, w, H, W))
+        if not (0 <= top <= h - 1 and 0 <= H - h - top <= h - 1):
+            raise ValueError("fit: pad rows: top %d and bottom %d outside 0 .. h - 1 = %d" % (top, H - h - top, h - 1))
+        if not (0 <= left <= w - 1 and 0 <= W - w - left <= w - 1):
+            raise ValueError("fit: pad columns: left %d and right %d outside 0 .. w - 1 = %d" % (left, W - w - left, w - 1))
+    elif mode == "crop":
+        if H > h or W > w:
+            raise ValueError("fit: crop of %d x %d to a larger %d x %d" % (h, w, H, W))
+        if not (0 <= top <= h - H and 0 <= left <= w - W):
+            raise ValueError("fit: crop window at top %d, left %d of %d x %d leaves the plane %d x %d" % (top, left, H, W, h, w))
+    elif top or left:
+        raise ValueError("fit: resize takes top = left = 0 (got %d, %d)" % (top, left))
+    _req(x, "x"); _req(out, "out")
+    shape = tuple(x.shape[:-2]) + (H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError("fit: out must be %s (got shape %s)" % (shape, tuple(out.shape)))
+    with _Rec("fit", nbytes=4.0 * (x.numel() + out.numel())):
+        check(lib().pu_fit(x.data_ptr(), out.data_ptr(), x.numel() // (h * w), h, w, H, W, FIT_MODES[mode], top, left,
+                           _stream()), "pu_fit")
     return out
 
 

@@ -22,6 +22,11 @@ With an augmentation plan (punet/augment.py) slot k also carries the batch's row
 and it is the augmented pair that the compute stream reads, so the wait on ``consumed[k]`` comes before
 that launch; the raw pair is touched by the copy stream alone.  The kernel runs under the previous step
 like the copies do.
+
+With a fit (punet/fit.py: the net's side is not the data's) slot k has one more pair of device buffers at the
+net's size, filled by ``fit.to_net`` on the copy stream from the augmented pair, or from the raw pair when
+there is no plan - again after the wait on ``consumed[k]``, since the fitted pair is then the one the compute
+stream reads.  Host arrays, pinned slots and the augmentation stay at the data size.
 """
 import numpy as np
 import torch
@@ -37,9 +42,11 @@ class BatchPrefetcher:
     times (the trainer consumes them within its step).
 
     augment: None, or an AugmentPlan over the samples of X: sample i of epoch e (set_epoch) is yielded
-    transformed by row i of plan.table(e), image and mask alike, whatever batch it is in."""
+    transformed by row i of plan.table(e), image and mask alike, whatever batch it is in.
+    fit: None, or a FitSpec for the H x W of X: the yielded batches are fit.to_net of the above, image and
+    mask alike, at the net's side."""
 
-    def __init__(self, X, Y, ranges, device, depth=2, augment=None):
+    def __init__(self, X, Y, ranges, device, depth=2, augment=None, fit=None):
         self.X, self.Y = X, Y
         self.ranges = list(ranges)
         self.device = torch.device(device)
@@ -72,6 +79,15 @@ class BatchPrefetcher:
             self.rows_dev = [torch.empty((bmax, 4), dtype=torch.int32, device=self.device) for _ in range(self.depth)]
             self.aug = [(torch.empty_like(dx), torch.empty_like(dy)) for dx, dy in self.dev]
             self.set_epoch(0)
+        self.fit = fit if fit else None
+        if self.fit is not None and bmax:
+            if len(xs) < 2 or len(ys) < 2 or tuple(xs[-2:]) != (self.fit.h, self.fit.w) or tuple(ys[-2:]) != tuple(xs[-2:]):
+                raise ValueError("fit: X and Y must end in the spec's %d x %d (got %s and %s)" % (
+                    self.fit.h, self.fit.w, (len(X),) + xs, (len(Y),) + ys))
+            side = (self.fit.side, self.fit.side)
+            self.fitted = [(torch.empty((bmax,) + xs[:-2] + side, dtype=torch.float32, device=self.device),
+                            torch.empty((bmax,) + ys[:-2] + side, dtype=torch.float32, device=self.device))
+                           for _ in range(self.depth)]
 
     def __len__(self):
         return len(self.ranges)
@@ -88,6 +104,19 @@ class BatchPrefetcher:
         rows = self.rows_dev[k][:n] if self.gpu else self.table[lo:lo + n]
         planes = (lambda v: v[:n].unsqueeze(1)) if dy.dim() == 3 else (lambda v: v[:n])
         K.augment(dx[:n], planes(dy), rows, self.plan.max_shift, out=(ax[:n], planes(ay)))
+
+    def _ready(self, k):
+        """the pair of slot k that the compute stream reads: fitted, else augmented, else as copied"""
+        if self.fit is not None:
+            return self.fitted[k]
+        return self.dev[k] if self.plan is None else self.aug[k]
+
+    def _fit(self, k, n):
+        """augmented (or raw) slot k -> fitted slot k, on the current stream"""
+        sx, sy = self.dev[k] if self.plan is None else self.aug[k]
+        fx, fy = self.fitted[k]
+        self.fit.to_net(sx[:n], out=fx[:n])
+        self.fit.to_net(sy[:n], out=fy[:n])
 
     def _fill(self, i):
         """stage batch i into its pinned slot and issue its H2D copy"""
@@ -107,6 +136,8 @@ class BatchPrefetcher:
             dy[:n].copy_(hy[:n])
             if self.plan is not None:
                 self._augment(k, lo, n)
+            if self.fit is not None:
+                self._fit(k, n)
             return
         with torch.cuda.stream(self.stream):
             if self.consumed[k] is not None:
@@ -116,6 +147,8 @@ class BatchPrefetcher:
             if self.plan is not None:
                 self.rows_dev[k][:n].copy_(self.rows_host[k][:n], non_blocking=True)
                 self._augment(k, lo, n)             # after the wait on consumed[k]: compute reads the augmented pair
+            if self.fit is not None:
+                self._fit(k, n)                     # likewise: compute reads the fitted pair
             self.copied[k].record(self.stream)
         self.pinned_busy[k] = self.copied[k]
 
@@ -139,7 +172,7 @@ class BatchPrefetcher:
             n = hi - lo
             if self.gpu:
                 torch.cuda.current_stream(self.device).wait_event(self.copied[k])
-            dx, dy = self.dev[k] if self.plan is None else self.aug[k]
+            dx, dy = self._ready(k)
             yield dx[:n], dy[:n]
             if self.gpu:
                 ev = torch.cuda.Event()

@@ -19,6 +19,10 @@ save checkpoints (:153-203).  Differences, all opt-in:
                    random (dy, dx) within +-S with reflected borders and mirrored left-right at random, image
                    and mask alike, on the device (punet/augment.py; rows seeded by --augment-seed, default
                    --seed); validation data is never augmented
+  --fit MODE --net-size S   the data keep their size (101 x 101) and the net is built at side S (128): every training
+                   batch, image and mask alike, is reflect-padded (pad) or resized (resize) to S on the device after
+                   the augmentation, the training loss is taken at S, and validation scores the predictions brought
+                   back to the data size (punet/fit.py); resize makes the masks non-binary, so it refuses a Lovasz loss
   --resident       keep the whole training set in HBM; default: batches stream host -> HBM through
                    pinned, double-buffered asynchronous copies (punet/loader.py) under the previous step
 Data-parallel training: launch with torch.distributed.run; each rank trains its contiguous shard
@@ -47,6 +51,7 @@ from punet import dp  # noqa: E402
 from punet import kernels as K  # noqa: E402
 from punet.augment import AugmentPlan, parse_augment  # noqa: E402
 from punet.engine import Trainer  # noqa: E402
+from punet.fit import parse_fit  # noqa: E402
 from punet.loader import BatchPrefetcher  # noqa: E402
 from eval import eval_net  # noqa: E402
 
@@ -91,18 +96,31 @@ def train(net, X_train, X_val, y_train, y_val, params):
     if spec:
         seed = params.get("augment_seed")
         plan = AugmentPlan(spec, samples_count, int(seed) if seed is not None else 0)
+    # the net's side differs from the data's: batches are fitted after the augmentation, predictions brought back
+    fit = parse_fit(params.get("fit"), tuple(np.shape(X_train)[-2:]), params.get("net_size")) or None
+    if fit is not None and fit.mode == "resize" and "lovasz" in params.get("loss", "bce"):
+        raise ValueError("fit: a resized mask is not binary, which the Lovasz loss needs - use --fit pad or --loss bce")
     prefetch = params.get("prefetch", True)
     if prefetch:
         # stream batches host -> HBM (pinned, double-buffered, overlapping the previous step)
-        batches = BatchPrefetcher(X_train, y_train, ranges, device, augment=plan)
+        batches = BatchPrefetcher(X_train, y_train, ranges, device, augment=plan, fit=fit)
     else:
         # the whole training set resident in HBM (copied once)
         X_dev = torch.from_numpy(np.asarray(X_train, dtype=np.float32)).to(device)
         Y_dev = torch.from_numpy(np.asarray(y_train, dtype=np.float32)).to(device)
-        if plan is None:
+        if plan is None and fit is None:
             batches = [(X_dev[lo:hi], Y_dev[lo:hi]) for lo, hi in ranges]
-        elif Y_dev.dim() == 3:
+        elif plan is not None and Y_dev.dim() == 3:
             Y_dev = Y_dev.unsqueeze(1)              # [N, H, W] masks as one plane per sample (batches: per epoch)
+
+        def resident_batch(lo, hi, rows):
+            # a batch slice augmented by its rows of the epoch's table, then fitted to the net's side
+            x, y = X_dev[lo:hi], Y_dev[lo:hi]
+            if rows is not None:
+                x, y = K.augment(x, y, rows[lo:hi], plan.max_shift)
+            if fit is not None:
+                x, y = fit.to_net(x), fit.to_net(y)
+            return x, y
     if params["stop_time"] > 0 and verbose:
         print("Training started at: [%s] and set to stop at: [%s]" % (
             datetime.fromtimestamp(time.time()).strftime("%B %d, %Y %H:%M:%S"),
@@ -112,10 +130,10 @@ def train(net, X_train, X_val, y_train, y_val, params):
         epoch_start_time = time.time()
         if prefetch:
             batches.set_epoch(epoch)
-        elif plan is not None:
-            # the epoch's rows go up once; each batch slice is augmented as the loop reaches it
-            rows = torch.from_numpy(plan.table(epoch)).to(device)
-            batches = (K.augment(X_dev[lo:hi], Y_dev[lo:hi], rows[lo:hi], plan.max_shift) for lo, hi in ranges)
+        elif plan is not None or fit is not None:
+            # the epoch's rows go up once; each batch slice is augmented and fitted as the loop reaches it
+            rows = torch.from_numpy(plan.table(epoch)).to(device) if plan is not None else None
+            batches = (resident_batch(lo, hi, rows) for lo, hi in ranges)
         seq = getattr(net, "hebb_mode", "slots") == "sequential"
         # trace reset per epoch (train.py:88): per-slot traces, or one trace threaded through
         hebb = net.initialZeroHebb() if seq else net.initialZeroHebb(bs)
@@ -178,7 +196,7 @@ def train(net, X_train, X_val, y_train, y_val, params):
                   % (epoch_loss, epoch_time, terminate))
         if (epoch + 1) % params["val_every"] == 0 or terminate:
             # every rank calls it: the chunks are dealt to the ranks and merged, each evaluated once
-            val_acc, val_loss = eval_net(net, X_val, y_val, device)
+            val_acc, val_loss = eval_net(net, X_val, y_val, device, fit=fit)
             val_train_losses.append(epoch_loss)
             val_test_losses.append(val_loss)
             val_accuracies.append(val_acc)
@@ -214,7 +232,10 @@ def start_train(x_train, x_valid, y_train, y_valid, out_dir, model, img_width, i
                 save_every=100, gamma=0.666, steplr=1e6, rollout=50000, prule="hebb", debug=False,
                 model_type="unetpres", depth=5, base_ch=8, neurons=16, batch_size=1, hebb_mode="slots",
                 batch_norm=False, bilinear_upsample=False, prefetch=True, bptt=0, clip_grad=0.0, loss="bce",
-                lovasz_weight=1.0, augment="", augment_seed=None):
+                lovasz_weight=1.0, augment="", augment_seed=None, fit="", net_size=None):
+    if bool(fit) != (net_size is not None):
+        raise ValueError("--fit and --net-size go together (got fit %r, net size %r)" % (fit, net_size))
+    side = int(net_size) if fit else img_width          # the net's side; the data keep img_height x img_width
     world, rank, local = dp.init_from_env()
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
@@ -224,13 +245,13 @@ def start_train(x_train, x_valid, y_train, y_valid, out_dir, model, img_width, i
               "gamma": gamma, "steplr": steplr, "prule": prule, "im_width": img_width, "im_height": img_height,
               "im_chan": img_chan, "debug": debug, "batch_size": batch_size, "prefetch": prefetch,
               "bptt": bptt, "clip_grad": clip_grad, "loss": loss, "lovasz_weight": lovasz_weight,
-              "augment": augment, "augment_seed": augment_seed}
+              "augment": augment, "augment_seed": augment_seed, "fit": fit, "net_size": net_size}
     if model_type == "unetp":
-        net = UNetp(n_channels=img_chan, n_classes=1, nbf=img_width, batch_norm=batch_norm,
+        net = UNetp(n_channels=img_chan, n_classes=1, nbf=side, batch_norm=batch_norm,
                     bilinear_upsample=bilinear_upsample, device=device, rule=prule, depth=depth, base_ch=base_ch,
                     hebb_mode=hebb_mode, trace_grad=bptt > 0)
     else:
-        net = UNetpRes(n_channels=img_chan, n_classes=1, nbf=img_width, batch_norm=batch_norm,
+        net = UNetpRes(n_channels=img_chan, n_classes=1, nbf=side, batch_norm=batch_norm,
                        bilinear_upsample=bilinear_upsample, device=device, rule=prule, neurons=neurons,
                        hebb_mode=hebb_mode, trace_grad=bptt > 0)
     if load:
@@ -294,6 +315,10 @@ def parse_args(argv=None):
                            "shift:S (random translation by up to S pixels each way, reflected borders); '': off")
     parser.add_option('--augment-seed', dest='augment_seed', type='int', default=None,
                       help='seed of the augmentation rows (default: --seed)')
+    parser.add_option('--fit', dest='fit', default='', choices=['', 'pad', 'resize'],
+                      help="train a net of side --net-size on data of --img-size: each batch, image and mask alike, is "
+                           "reflect-padded (pad) or resized (resize) on the device, validation is scored at --img-size")
+    parser.add_option('--net-size', dest='net_size', type='int', default=None, help="the net's side with --fit")
     parser.add_option('--seed', dest='seed', type='int', default=0)
     parser.add_option('--resident', dest='resident', action='store_true', default=False,
                       help='copy the whole training set to HBM once instead of streaming batches')
@@ -333,4 +358,5 @@ if __name__ == '__main__':
                 neurons=args.neurons, batch_size=args.batch_size, hebb_mode=args.hebb_mode,
                 batch_norm=args.batch_norm, bilinear_upsample=args.bilinear, prefetch=not args.resident,
                 bptt=args.bptt, clip_grad=args.clip_grad, loss=args.loss, lovasz_weight=args.lovasz_weight,
-                augment=args.augment, augment_seed=args.seed if args.augment_seed is None else args.augment_seed)
+                augment=args.augment, augment_seed=args.seed if args.augment_seed is None else args.augment_seed,
+                fit=args.fit, net_size=args.net_size)
